@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- HOGAN G+D training-step throughput on synthetic 256x256 hand-object-pose tensors.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+      A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds the other legs: the step in
+      the other form (captured hipGraph / eager), host issue time, the dominant kernel's roofline, the generator-forward
+      latency and the CPU baseline.  --dump-outputs DIR writes what the last timed step left its caller (loss terms, G's and
+      D's parameters) as .npy files, so that two builds can be compared output for output; that step then starts from the
+      seeded initial weights and optimiser state (restored outside the timed interval), so that it is the same in every run.
       N>1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run
       --nproc-per-node N ... bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE in the environment), or -- when
       WORLD_SIZE is not set -- this script starts that launcher itself as a CHILD process before touching the GPU and
@@ -173,6 +178,47 @@ def gen_forward_latency(opt, batch, side, iters=10):
     return out
 
 
+DUMP_MAX_ELEMS = 6 << 20          # per parameter vector: 24 MB of float32; G and D together stay under 64 MB
+
+
+def training_state(model):
+    """(parameter tree, optimiser) of G and D: what a training step reads besides its batch and the frozen VGG."""
+    return [(model._net(model._G), model._optimizer_G), (model._net(model._D), model._optimizer_D)]
+
+
+def snapshot_state(model):
+    return [tree.flat.clone() for tree, _ in training_state(model)]
+
+
+def restore_state(model, snap):
+    """Back to the state `snap` was taken in, before any optimiser step: the weights (their operand planes are re-made on the next
+    step: version bump) and a fresh Adam (zero moments, step count 0, uploaded by the next step)."""
+    for (tree, opt), flat in zip(training_state(model), snap):
+        tree.flat.copy_(flat)
+        tree.version += 1
+        opt.exp_avg.zero_()
+        opt.exp_avg_sq.zero_()
+        opt.step_count = 0
+
+
+def dump_outputs(out_dir, model, errors):
+    """--dump-outputs: what the last timed step (`optimize_parameters`) hands its caller -- the loss terms of
+    `get_current_errors()` (loss_<name>.npy, float64) and G's and D's parameters after their Adam updates (params_G.npy,
+    params_D.npy, float32, the flat parameter buffers).  A buffer larger than DUMP_MAX_ELEMS is written as a fixed sample
+    of its elements: DUMP_MAX_ELEMS positions drawn with a seeded generator (seed 0 for G, 1 for D), sorted."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in errors.items():
+        np.save(os.path.join(out_dir, 'loss_%s.npy' % k), np.array([v], dtype=np.float64))
+    for seed, (tag, net) in enumerate((('G', model._G), ('D', model._D))):
+        flat = model._net(net).flat.detach()
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(seed))
+            flat = flat[idx.sort().values.to(flat.device)]
+        np.save(os.path.join(out_dir, 'params_%s.npy' % tag), flat.float().cpu().numpy())
+
+
 def usable_cores():
     """Host cores this process may really use: scheduler affinity capped by the cgroup CPU quota (a thread pool
     sized from os.cpu_count() inside a quota-limited container oversubscribes badly)."""
@@ -325,11 +371,16 @@ def main():
     ap.add_argument('--precision', default=os.environ.get('HOIG_PRECISION', 'bf16x3:f16x2'),
                     help="'<forward>[:<data gradient>[:<weight gradient>]]' of f32 | bf16x3 | f16x2 | bf16; f16f6 = forward on fp16 + block-scaled fp6 terms, backward f16x2: "
                          "faster, outputs inside 1e-3, but its worst gradient tensor exceeds 3e-2 at 256x256 (profiles/r03_grad_parity_256.txt), so it is opt-in (hoig_amd/ops.py set_precision)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the comparison leg in the other step form, host issue time, the dominant kernel\'s roofline, '
+                         'the generator-forward latency and the CPU baseline (the options below that name these legs apply to it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss terms and G\'s and D\'s parameters after the last timed step to DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--graph', action='store_true', help='time the step as a replayed hipGraph (default: issued kernel by kernel on its streams, which is faster on this ROCm: DESIGN.md section 3c)')
-    ap.add_argument('--graph-steps', type=int, default=20, help='steps of the comparison leg in the OTHER form (captured if the main run is eager, and vice versa); 0 = skip')
+    ap.add_argument('--graph-steps', type=int, default=20, help='--full: steps of the comparison leg in the OTHER form (captured if the main run is eager, and vice versa); 0 = skip')
     ap.add_argument('--no-gen-fwd', action='store_true')
-    ap.add_argument('--host-samples', type=int, default=5, help='warmed samples of the host issue time per step (median reported); 0 = one plain step (profiling runs)')
+    ap.add_argument('--host-samples', type=int, default=5, help='--full: warmed samples of the host issue time per step (median reported); 0 = one plain step (profiling runs)')
     ap.add_argument('--fwd-batch', type=int, default=32, help='batch of the generator-forward latency leg')
     ap.add_argument('--cpu-baseline-worker', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-budget', type=int, default=150, help='wall seconds the CPU-baseline child may use')
@@ -370,6 +421,7 @@ def main():
     model.set_train()
     inputs = synthetic.make_inputs(args.batch, args.side, seed=8 + rank, dataset=args.dataset)
     model.set_input(inputs)
+    initial = snapshot_state(model) if args.dump_outputs else None
     torch.cuda.synchronize()
 
     def barrier():
@@ -385,16 +437,29 @@ def main():
     for _ in range(args.warmup):
         model.optimize_parameters()
     barrier()
+    paused = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            # --dump-outputs: the last timed step starts from the seeded initial weights and a fresh optimiser.  Every step sums
+            # in fp32 atomics (norm statistics, split weight gradients, loss reductions), so runs differ by rounding per step,
+            # and training on -- Adam normalises tiny gradients to full-size updates -- grows that far beyond rounding: only a
+            # step from a fixed state computes the same outputs from the same inputs in every run.  (Not timed.)
+            barrier()
+            tp = time.perf_counter()
+            restore_state(model, initial)
+            barrier()
+            paused += time.perf_counter() - tp
         model.optimize_parameters()
     barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     if ddp:
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     errors = model.get_current_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, errors)
     is_captured = lambda: bool(model._graphs) and all(g['graphs'] is not None for g in model._graphs.values())
     main_captured = is_captured()
 
@@ -418,31 +483,31 @@ def main():
         ts = sorted(ts[2:])
         return ts[len(ts) // 2]
 
-    other_ms, other_host_ms = None, None
-    if args.graph_steps > 0:                       # the same step in the other form, same process, same weights
-        model._use_graph = not args.graph
-        model.set_input(inputs)                    # (a captured step reads its inputs from staging buffers made by set_input)
-        for _ in range(trainer_mod._GRAPH_WARMUP + 2):
-            model.optimize_parameters()
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(args.graph_steps):
-            model.optimize_parameters()
-        barrier()
-        other_ms = (time.perf_counter() - t1) / args.graph_steps * 1e3
-        other_host_ms = host_issue_ms()
-        other_captured = is_captured()
-        model._use_graph = bool(args.graph)
-        model.set_input(inputs)
-        for _ in range(trainer_mod._GRAPH_WARMUP + 2):      # back in the main form, warmed again
-            model.optimize_parameters()
-        barrier()
-    main_host_ms = host_issue_ms()
+    other_ms, other_host_ms, main_host_ms = None, None, None
+    if args.full:
+        if args.graph_steps > 0:                       # the same step in the other form, same process, same weights
+            model._use_graph = not args.graph
+            model.set_input(inputs)                    # (a captured step reads its inputs from staging buffers made by set_input)
+            for _ in range(trainer_mod._GRAPH_WARMUP + 2):
+                model.optimize_parameters()
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.graph_steps):
+                model.optimize_parameters()
+            barrier()
+            other_ms = (time.perf_counter() - t1) / args.graph_steps * 1e3
+            other_host_ms = host_issue_ms()
+            other_captured = is_captured()
+            model._use_graph = bool(args.graph)
+            model.set_input(inputs)
+            for _ in range(trainer_mod._GRAPH_WARMUP + 2):      # back in the main form, warmed again
+                model.optimize_parameters()
+            barrier()
+        main_host_ms = host_issue_ms()
 
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = world * args.batch * args.steps / dt
-        roof = None if os.environ.get('HOIG_BENCH_NO_ROOF') else dominant_kernel_roofline(args.batch, args.side, args.precision)
         out = {
             'metric': 'HOGAN train images/sec at %dx%d' % (args.side, args.side),
             'value': round(value, 3), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -455,21 +520,25 @@ def main():
                        'global_batch': world * args.batch, 'parallelism': 'dp%d' % world},
             'step_tflops': round(GFLOP_PER_PAIR_TRAIN_256 * (args.side / 256.0) ** 2 * value / 1e3, 2),
             'step_form': 'captured hipGraph replay' if main_captured else 'eager: kernels issued on the step\'s HIP streams',
-            'host_ms_per_step_idle_device': round(main_host_ms, 2),
-            'hipgraph': None if other_ms is None else {
-                'form': 'eager' if args.graph else 'captured hipGraph replay',
-                'captured_step': bool(other_captured) if not args.graph else main_captured,
-                'ms_per_step': round(other_ms, 3), 'value': round(world * args.batch / (other_ms * 1e-3), 3),
-                'host_ms_per_step_idle_device': round(other_host_ms, 2)},
-            'roofline': roof,
             'losses_finite': all(v == v and abs(v) != float('inf') for v in errors.values()),
         }
-        model = None
-        torch.cuda.empty_cache()
-        if world == 1 and not args.no_gen_fwd:
-            out['gen_fwd'] = gen_forward_latency(opt, args.fwd_batch, args.side)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(args.side, args.cpu_budget)
+        if args.full:
+            roof = None if os.environ.get('HOIG_BENCH_NO_ROOF') else dominant_kernel_roofline(args.batch, args.side, args.precision)
+            out.update({
+                'host_ms_per_step_idle_device': round(main_host_ms, 2),
+                'hipgraph': None if other_ms is None else {
+                    'form': 'eager' if args.graph else 'captured hipGraph replay',
+                    'captured_step': bool(other_captured) if not args.graph else main_captured,
+                    'ms_per_step': round(other_ms, 3), 'value': round(world * args.batch / (other_ms * 1e-3), 3),
+                    'host_ms_per_step_idle_device': round(other_host_ms, 2)},
+                'roofline': roof,
+            })
+            model = None
+            torch.cuda.empty_cache()
+            if world == 1 and not args.no_gen_fwd:
+                out['gen_fwd'] = gen_forward_latency(opt, args.fwd_batch, args.side)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(args.side, args.cpu_budget)
         print(json.dumps(out))
     if ddp:
         dist.destroy_process_group()

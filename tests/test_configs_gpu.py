@@ -163,14 +163,14 @@ def test_config2_256_forward_and_step():
 
 def test_bench_line_contract():
     """bench.py's ONE JSON line (the driver's contract): the keys, the timed-step bookkeeping, the roofline object of the dominant
-    kernel measured live, and the gen-fwd leg -- on a short run (2 timed steps, no CPU-baseline child)."""
+    kernel measured live, and the gen-fwd leg -- on a short --full run (2 timed steps, no CPU-baseline child)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline',
                         '--fwd-batch', '8', '--graph-steps', '2'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -190,6 +190,37 @@ def test_bench_line_contract():
     assert d['hipgraph']['captured_step'] is True and d['hipgraph']['ms_per_step'] > 0 and d['step_form'].startswith('eager')
     assert d['gen_fwd']['finite'] and d['gen_fwd']['batch'] == 8 and d['losses_finite'] is True
     assert 'cpu_baseline' not in d or d['cpu_baseline'] is None or isinstance(d['cpu_baseline'], dict)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times its steps and prints the headline line only; --dump-outputs writes the last timed
+    step's loss terms and G's and D's parameters as float32 / float64 .npy files, 64 MB at most."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs',
+                        str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['metric'].startswith('HOGAN train images/sec at 256') and d['unit'] == 'images/s' and d['higher_is_better'] is True
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] and d['losses_finite'] is True
+    assert abs(d['value'] - 8 / (d['ms_per_step'] * 1e-3)) < 0.02 * d['value']
+    for k in ('roofline', 'hipgraph', 'gen_fwd', 'cpu_baseline', 'host_ms_per_step_idle_device'):
+        assert k not in d, k
+    files = sorted(os.listdir(str(tmp_path)))
+    assert 'params_G.npy' in files and 'params_D.npy' in files and 'loss_g_rec.npy' in files and 'loss_d_fake.npy' in files
+    total = 0
+    for f in files:
+        a = np.load(str(tmp_path / f))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.abs(np.load(str(tmp_path / 'params_G.npy'))).max() > 0
 
 
 def test_config2_gradients_256_against_oracle():

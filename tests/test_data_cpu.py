@@ -239,23 +239,16 @@ def test_imread_matches_cv2_when_available(tmp_path):
 
 def test_host_files_are_not_the_references(tmp_path):
     """the loader's host half keeps the reference's NAMES; its bodies are this package's own.  No file of hoig_amd/data shares
-    more than a quarter of its non-trivial lines with a file of the reference's data packages (build container only)."""
+    more than a quarter of its non-trivial lines with a file of the reference's data packages (compared through the line digests of
+    tests/golden/reference_data_lines.npz, made by tests/golden/make_golden_live_pins.py data_lines)."""
     import glob
     import os
-    refs = glob.glob('/root/reference/*/data/*.py')
-    if not refs:
-        pytest.skip('no reference checkout')
-
-    def lines(p):
-        out = []
-        for l in open(p):
-            l = l.strip()
-            if len(l) >= 12 and not l.startswith(('#', 'import ', 'from ')):
-                out.append(l)
-        return out
-    ref_lines = [set(lines(r)) for r in refs]
+    from common import line_digests, load_golden
+    g = load_golden('reference_data_lines.npz')
+    ref_lines = [set(g[k].tolist()) for k in g.files]
+    assert len(ref_lines) >= 2 and all(ref_lines)
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hoig_amd', 'data')
     for f in glob.glob(os.path.join(root, '*.py')):
-        mine = lines(f)
+        mine = line_digests(f).tolist()
         share = max(sum(1 for l in mine if l in r) for r in ref_lines) / max(1, len(mine))
         assert share <= 0.25, (f, share)

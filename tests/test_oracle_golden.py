@@ -7,6 +7,19 @@ import torch
 from common import oracle_trainer, load_golden, OUT_NAMES
 
 
+# The fixtures were recorded with 8 intra-op threads.  CPU convolutions split their fp32 sums by thread count, and two steps of
+# a GAN carry those orderings past this file's tolerances on some counts (1, 3, 5, 6, 7 on an 8-core host): run at 8 always.
+GOLDEN_THREADS = 8
+
+
+@pytest.fixture(autouse=True)
+def _golden_threads():
+    prev = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(prev)
+
+
 GOLDEN = [('generator_spade_attn', 'hov3_spade_attn_64.npz'), ('generator_spade', 'hov3_spade_64.npz'),
           ('generator_spade_attn_tiny', 'hov3_spade_attn_tiny_64.npz'), ('generator_base', 'hov3_base_64.npz'),
           ('generator_spade_attn', 'dexycb_spade_attn_64.npz')]

@@ -9,7 +9,7 @@ python -c "from hoig_amd import _lib; _lib.lib" || { echo "library does not load
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 3000 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/${TAG}_pytest_gpu.log
 fi
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 export TMPDIR=/tmp
 cd /tmp
 HOIG_WGRAD_STREAM=0 HOIG_STREAMS=0 HOIG_BENCH_NO_ROOF=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_serial -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gen-fwd --graph-steps 0 --host-samples 0 > /dev/null 2>&1

@@ -11,7 +11,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   # the opt-in duplicates too (the exact-fp32 gradient comparison at 128x128 lives there), once per round
   ( time timeout 2400 python -m pytest tests -m gpu_slow -q 2>&1 | tail -8 ) > $O/${TAG}_pytest_gpu_slow.log 2>&1
 fi
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 export TMPDIR=/tmp
 cd /tmp
 HOIG_WGRAD_STREAM=0 HOIG_STREAMS=0 HOIG_BENCH_NO_ROOF=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_serial -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gen-fwd --graph-steps 0 --host-samples 0 > /dev/null 2>&1
