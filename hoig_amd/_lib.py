@@ -17,6 +17,7 @@ OK, EINVAL, ELAUNCH, EUNSUPPORTED = 0, -1, -2, -3
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16X2, PREC_F16F6 = 0, 1, 2, 3, 4
 LOSS_L1, LOSS_MSE, LOSS_BCE = 0, 1, 2
+POOL_MAX, POOL_AVG = 0, 1
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
 
 
@@ -146,6 +147,12 @@ _SIGS = {
     'hoig_prep_texture_batched': [_i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'hoig_prep_lookup_batched': [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'hoig_mano_lbs': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp],
+    'hoig_pool2d_fwd': [_vp, _vp] + [_i] * 10 + [_vp],
+    'hoig_stage_images_u8': [_vp, _vp] + [_i] * 7 + [_vp, _vp],
+    'hoig_pad2d': [_vp, _vp] + [_i] * 6 + [_vp],
+    'hoig_global_avgpool': [_vp, _vp, _i, _i, _i, _vp],
+    'hoig_lpips_layer': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    'hoig_ssim': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp],
 }
 
 
@@ -177,6 +184,10 @@ def _load():
     lib.hoig_stream_scratch_bytes.restype = ctypes.c_int64
     lib.hoig_conv2d_bwd_weight_scratch_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.hoig_conv2d_bwd_weight_scratch_bytes.restype = ctypes.c_int64
+    lib.hoig_lpips_workspace_bytes.argtypes = [_i, _i]
+    lib.hoig_lpips_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_ssim_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
+    lib.hoig_ssim_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_version.argtypes = []
     lib.hoig_version.restype = ctypes.c_char_p
     return lib

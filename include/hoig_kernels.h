@@ -601,6 +601,39 @@ int hoig_mano_lbs(const float *v_template, const float *shapedirs, const float *
                   const float *betas, const float *transl /*nullable*/, float *verts, int ld_v, float *joints /*nullable*/, int B,
                   hoig_stream_t stream);
 
+/* ---- EVALUATION METRICS (forward only; hoig_amd/csrc/metrics.hip, hoig_amd/metrics): FID's InceptionV3 (metrics/pytorch_fid/
+ *      inception.py), LPIPS-AlexNet (metrics/lpips.py) and SSIM / MS-SSIM (metrics/ssim.py through pytorch_msssim 0.2.1).  The
+ *      networks' convolutions run on hoig_conv2d_fwd (bias + ReLU in its epilogue).  Reductions are deterministic: per-workgroup
+ *      partials in the caller's workspace, summed in a fixed order by the last workgroup of an image to arrive (an integer ticket per
+ *      image); the workspace must be zero-filled once before its first use and is left zero-filled by every call. ---- */
+enum { HOIG_POOL_MAX = 0, HOIG_POOL_AVG = 1 };
+/* F.max_pool2d / F.avg_pool2d(k, stride, padding=(pad_h, pad_w), count_include_pad), floor output size, NHWC [B,H,W,C] ->
+ * [B,Ho,Wo,C] with Ho = (H + 2 pad_h - k) / stride + 1; pad <= k / 2 */
+int hoig_pool2d_fwd(const float *x, float *y, int B, int H, int W, int C, int k, int stride, int pad_h, int pad_w, int mode,
+                    int count_include_pad, hoig_stream_t stream);
+/* uint8 [B,Hi,Wi,C] (C <= 4) -> fp32 NHWC [B,Ho,Wo,C]: v = u8 / 255 (ToTensor), bilinear resize with align_corners=False when
+ * (Ho,Wo) != (Hi,Wi) (F.interpolate), then n_affine (0..2) per-channel steps v = (v - sub[c]) / div[c] in order.  affine: HOST
+ * memory, n_affine x [sub[C] | div[C]] (read at the call: a captured launch keeps the values) */
+int hoig_stage_images_u8(const uint8_t *src, float *y, int B, int Hi, int Wi, int C, int Ho, int Wo, int n_affine, const float *affine,
+                         hoig_stream_t stream);
+/* zero-padded copy [B,H,W,C] -> [B,H+2pad_h,W+2pad_w,C] (the asymmetric paddings of Inception's 1x7 / 7x1 / 1x3 / 3x1 layers, which
+ * then run on hoig_conv2d_fwd with pad 0); C % 4 == 0, HOIG_EUNSUPPORTED otherwise */
+int hoig_pad2d(const float *x, float *y, int B, int H, int W, int C, int pad_h, int pad_w, hoig_stream_t stream);
+/* y[b][c] = mean over the HW pixels of x[b][.][c] (adaptive_avg_pool2d to 1x1) */
+int hoig_global_avgpool(const float *x, float *y, int B, int HW, int C, hoig_stream_t stream);
+/* One LPIPS layer (lpips.py:8-9,64-74): per pixel x * rsqrt(sum_c x^2 + 1e-10) for fx and fy, squared difference, dot with the
+ * head's C weights w; out[b] += the mean of that over the HW pixels of image b.  fx, fy: [B,HW,C], C % 4 == 0 and C <= 512
+ * (HOIG_EUNSUPPORTED otherwise).  workspace: hoig_lpips_workspace_bytes(B, HW) bytes */
+int64_t hoig_lpips_workspace_bytes(int B, int HW);
+int hoig_lpips_layer(const float *fx, const float *fy, const float *w, float *out, int B, int HW, int C, void *workspace,
+                     hoig_stream_t stream);
+/* One SSIM level of pytorch_msssim 0.2.1 (_ssim): separable Gaussian window (win odd taps, sigma, normalised to sum 1), valid
+ * padding, C1 = (K1 data_range)^2, C2 = (K2 data_range)^2; ssim_out[b][c] / cs_out[b][c] = the means of the ssim and cs maps.
+ * x, y: [B,H,W,C], win <= 15 (HOIG_EUNSUPPORTED above).  workspace: hoig_ssim_workspace_bytes(B, H, W, C, win) bytes */
+int64_t hoig_ssim_workspace_bytes(int B, int H, int W, int C, int win);
+int hoig_ssim(const float *x, const float *y, float *ssim_out, float *cs_out, int B, int H, int W, int C, float data_range, float K1,
+              float K2, int win, float sigma, void *workspace, hoig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
