@@ -66,6 +66,15 @@ __device__ __forceinline__ float hoig_act_grad_from_y(float y, int act, float sl
     }
 }
 
+// The sums a convolution's epilogue leaves for the instance norm that reads its output (hoig_conv2d_fwd_packed_stats and its kin,
+// consumed by hoig_inorm_stats_from_sums): accumulators [b][moment 0 / 1][N] of DOUBLES inside the norm workspace's pool of fp32
+// accumulators (all-zero bits are zero in both formats, so the pool's contract -- zero on entry, zero on return -- covers them).
+// Several hundred fp32 atomics per address left about 1e-6 of relative error in sum y at 65536 pixels; in fp64 what remains is the
+// rounding of each workgroup's own fp32 partial.
+__device__ __forceinline__ void hoig_stats_add(double *stats, int b, int N, int mom, int n, float v) {
+    atomicAdd(stats + ((size_t)b * 2 + mom) * N + n, (double)v);
+}
+
 // XCD-aware remap of a 1-D block id: blocks b and b+8 share an XCD (round-robin dispatch), so give each
 // XCD a contiguous chunk of the logical tile order; bijective for any grid size (guide §5, T1).
 __device__ __forceinline__ int hoig_xcd_remap(int bid, int nblk) {

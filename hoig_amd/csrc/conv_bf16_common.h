@@ -122,7 +122,7 @@ struct HaloArgs {
     float *C_g2;
     int a_split;               // 1: A is a PRE-SPLIT tensor, per pixel [hi: Cg bf16][lo: Cg bf16] (hoig_split_planes_bf16): the 3x3
                                // stride-1 data gradient on conv_halo16.hip copies it to LDS without splitting (no A2 then)
-    float *stats;              // (nullable) [Bn][2][N] fp32 accumulators: += per-image, per-channel sum and sum of squares of the
+    double *stats;             // (nullable) [Bn][2][N] fp64 accumulators: += per-image, per-channel sum and sum of squares of the
                                // values written to C -- the statistics of the instance norm that reads C next
 };
 

@@ -67,7 +67,7 @@ struct F6Args {
     // >= in_relu_c0 (a multiple of 32), applied when the halo is converted; the zero padding stays zero
     const float *in_scale, *in_shift;
     int in_relu_c0;
-    float *stats;                             // nullable: per image [sum | sum of squares][N] of the stored values, atomically added
+    double *stats;                             // nullable: per image [sum | sum of squares][N] of the stored values, atomically added
 };
 
 __device__ __forceinline__ size_t plane_index(int n, int k, int K) {
@@ -486,13 +486,12 @@ __global__ __launch_bounds__(NT) void conv_halo3_f6_kernel(const F6Args p) {
             }
         }
         __syncthreads();
-        float *stats_img = p.stats + (size_t)b * 2 * p.N;
         for (int e = tid; e < 2 * BN; e += NT) {
             const int mom = e / BN, cl = e - mom * BN;
             float v = 0.f;
 #pragma unroll
             for (int k = 0; k < WM; ++k) v += red[(k * 2 + mom) * BN + cl];
-            atomicAdd(&stats_img[(size_t)mom * p.N + n0 + cl], v);
+            hoig_stats_add(p.stats, b, p.N, mom, n0 + cl, v);
         }
     }
 }
@@ -519,7 +518,7 @@ extern "C" int hoig_pack_conv_weight_f6(const float *w, int Co, int RS, int Ci, 
 // hoig_conv2d_fwd_packed with HOIG_PREC_BF16X3)
 static int launch_f6(const hoig_conv_desc *d, const float *x, const float *x2, int cg1, const uint16_t *w_hi, const uint8_t *q_hi,
                      const uint8_t *q_lo, const float *bias, float *y, hipStream_t st, const float *in_scale = nullptr,
-                     const float *in_shift = nullptr, int in_relu_c0 = 0, float *stats = nullptr) {
+                     const float *in_shift = nullptr, int in_relu_c0 = 0, double *stats = nullptr) {
     if (d->transposed || d->stride != 1 || d->R != 3 || d->S != 3 || d->pad != 1 || d->Hi != d->Ho || d->Wi != d->Wo)
         return HOIG_EUNSUPPORTED;
     if ((d->Ci & 63) || (d->Co & 63) || (d->Hi & 7) || (d->Wi & 31)) return HOIG_EUNSUPPORTED;
@@ -588,7 +587,7 @@ extern "C" int hoig_conv2d_cat_fwd_f6(const hoig_conv_desc *d, const float *x1, 
 // the gathered tensor applied in the loader; stats (nullable) = the per-image channel sums of y for the norm that follows
 extern "C" int hoig_conv2d_fwd_f6_ex(const hoig_conv_desc *d, const float *x, int C1, const float *x2, const uint16_t *w_hi,
                                      const uint8_t *q_hi, const uint8_t *q_lo, const float *bias, const float *in_scale,
-                                     const float *in_shift, int in_relu_c0, float *y, float *stats, hoig_stream_t stream) {
+                                     const float *in_shift, int in_relu_c0, float *y, double *stats, hoig_stream_t stream) {
     if (!d || !x || !w_hi || !q_hi || !q_lo || !y || (in_scale == nullptr) != (in_shift == nullptr) || in_relu_c0 < 0) return HOIG_EINVAL;
     return launch_f6(d, x, x2, x2 ? C1 : 0, w_hi, q_hi, q_lo, bias, y, (hipStream_t)stream, in_scale, in_shift, in_relu_c0, stats);
 }

@@ -379,7 +379,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_halo3_m16_kernel(const Halo
             }
         }
     }
-    if (p.stats) m16_stats_epilogue<NTW, WM, BN, NT>(st1, st2, smem, p.stats + (size_t)b * 2 * p.N, p.N, n0, wm, wn, lane, tid);
+    if (p.stats) m16_stats_epilogue<NTW, WM, BN, NT>(st1, st2, smem, p.stats, b, p.N, n0, wm, wn, lane, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(256) void conv_halo_s2_m16_kernel(const HaloArgs p)
             }
         }
     }
-    if (p.stats) m16_stats_epilogue<NTW, 2, BN, NT>(st1, st2, smem, p.stats + (size_t)b * 2 * p.N, p.N, n0, wm, wn, lane, tid);
+    if (p.stats) m16_stats_epilogue<NTW, 2, BN, NT>(st1, st2, smem, p.stats, b, p.N, n0, wm, wn, lane, tid);
 }
 
 template <int NS, int BN>

@@ -589,7 +589,7 @@ int hoig_conv_small_fwd_acts(const hoig_conv_desc *d, const float *x, const floa
 int hoig_conv_head7_m16(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, unsigned long long acts,
                         hipStream_t st);                  // conv_head16.hip
 // conv_thin.hip: stride-1 'same' convolutions with <= 8 (3x3: 16) channels on one side, taps in place of the missing channels
-int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st, float *stats = nullptr);
+int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st, double *stats = nullptr);
 int hoig_conv_thin_dgrad(const hoig_conv_desc *d, const float *dy, const float *w, float *dx, int accumulate, hipStream_t st);
 int hoig_conv_thin_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st);
 int hoig_conv_thin_out(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
@@ -632,7 +632,7 @@ extern "C" int hoig_conv2d_fwd(const hoig_conv_desc *d, const float *x, const fl
 // hoig_conv2d_fwd + the per-image channel sums of y for the instance norm that follows (include/hoig_kernels.h), for the layers
 // hoig_conv2d_fwd_packed_stats does not reach: the thin-INPUT convolutions (the 7x7 stems: 3 / 8 -> 64 channels at full resolution,
 // where the statistics pass re-reads the largest tensor of the network).  HOIG_EUNSUPPORTED otherwise.
-extern "C" int hoig_conv2d_fwd_stats(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, float *stats,
+extern "C" int hoig_conv2d_fwd_stats(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, double *stats,
                                      hoig_stream_t stream) {
     int rc = check_desc(d);
     if (rc) return rc;

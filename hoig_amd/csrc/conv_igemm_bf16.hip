@@ -505,7 +505,7 @@ int launch(Args a, int ns, hipStream_t st) {
 // loop), and the workgroup then issues ONE atomic per (channel, moment) into the image's accumulators -- as many per address as
 // the streaming statistics kernel it replaces issued (norm.hip: one per 16 pixel rows).
 template <int TN, int WM, int WN, int NT>
-__device__ __forceinline__ void halo_stats_epilogue(float (&s1)[TN], float (&s2)[TN], unsigned char *lds, float *stats_img, int N,
+__device__ __forceinline__ void halo_stats_epilogue(float (&s1)[TN], float (&s2)[TN], unsigned char *lds, double *stats, int b, int N,
                                                     int n0, int wm, int wn, int lane) {
     const int l31 = lane & 31, lh = lane >> 5;
 #pragma unroll
@@ -529,7 +529,7 @@ __device__ __forceinline__ void halo_stats_epilogue(float (&s1)[TN], float (&s2)
 #pragma unroll
         for (int k = 0; k < WM; ++k) v += red[(((k * WN + w) * TN + j) * 2 + m) * 32 + l];
         const int n = n0 + w * (TN * 32) + j * 32 + l;
-        if (n < N) atomicAdd(&stats_img[(size_t)m * N + n], v);
+        if (n < N) hoig_stats_add(stats, b, N, m, n, v);
     }
 }
 
@@ -1003,7 +1003,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_halo3_bf16_kernel(const Hal
             }
         }
     }
-    if (p.stats) halo_stats_epilogue<TN, WM, WN, NT>(st1, st2, smem, p.stats + (size_t)b * 2 * p.N, p.N, n0, wm, wn, lane);
+    if (p.stats) halo_stats_epilogue<TN, WM, WN, NT>(st1, st2, smem, p.stats, b, p.N, n0, wm, wn, lane);
 }
 
 template <int NS, int WM, int WN, int BN, int MODE>
@@ -1349,7 +1349,7 @@ __global__ __launch_bounds__(256) void conv_halo_s2_bf16_kernel(const HaloArgs p
             }
         }
     }
-    if (p.stats) halo_stats_epilogue<TN, 2, WN, NT>(st1, st2, smem, p.stats + (size_t)b * 2 * p.N, p.N, n0, wm, wn, lane);
+    if (p.stats) halo_stats_epilogue<TN, 2, WN, NT>(st1, st2, smem, p.stats, b, p.N, n0, wm, wn, lane);
 }
 
 // a: H, W = spatial size of the GATHERED tensor (gather mode: the fine grid, output is H/2 x W/2; scatter mode: the coarse
@@ -1421,7 +1421,7 @@ struct PairSet {
 
 int run(const hoig_conv_desc *d, const float *a, const unsigned short *wh, const unsigned short *wl, const float *bias,
         float *c, bool dgrad, hipStream_t st, const float *a2 = nullptr, int cg1 = 0, float *c2 = nullptr, int n1 = 0,
-        const float *addend = nullptr, float *stats = nullptr, bool a_split = false, const PairSet *g2 = nullptr,
+        const float *addend = nullptr, double *stats = nullptr, bool a_split = false, const PairSet *g2 = nullptr,
         const InNorm *in = nullptr) {
     if (in && (dgrad || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->transposed || a_split || g2))
         return HOIG_EUNSUPPORTED;
@@ -1613,14 +1613,14 @@ extern "C" int hoig_conv2d_bwd_data_packed(const hoig_conv_desc *d, const float 
 // y = conv(x) and, from the same epilogue, stats[b][0/1][co] += sum / sum of squares of y over image b (HOIG_EUNSUPPORTED where the
 // layer's kernel has no such epilogue: 3x3 stride-1 "same" and 3x3 stride-2 layers on the halo kernels have it)
 extern "C" int hoig_conv2d_fwd_packed_stats(const hoig_conv_desc *d, const float *x, const uint16_t *w_hi, const uint16_t *w_lo,
-                                            const float *bias, float *y, float *stats, hoig_stream_t stream) {
+                                            const float *bias, float *y, double *stats, hoig_stream_t stream) {
     if (!d || !x || !w_hi || !y || !stats) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     return run(d, x, w_hi, w_lo, bias, y, false, (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, stats);
 }
 extern "C" int hoig_conv2d_cat_fwd_packed_stats(const hoig_conv_desc *d, const float *x1, int C1, const float *x2,
                                                 const uint16_t *w_hi, const uint16_t *w_lo, const float *bias, float *y,
-                                                float *stats, hoig_stream_t stream) {
+                                                double *stats, hoig_stream_t stream) {
     if (!d || !x1 || !x2 || !w_hi || !y || !stats) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     return run(d, x1, w_hi, w_lo, bias, y, false, (hipStream_t)stream, x2, C1, nullptr, 0, nullptr, stats);
@@ -1630,7 +1630,7 @@ extern "C" int hoig_conv2d_cat_fwd_packed_stats(const hoig_conv_desc *d, const f
 // applies x * in_scale + in_shift per (image, gathered channel) and ReLU on channels >= in_relu_c0 (include/hoig_kernels.h)
 extern "C" int hoig_conv2d_fwd_packed_normin(const hoig_conv_desc *d, const float *x, int C1, const float *x2, const uint16_t *w_hi,
                                              const uint16_t *w_lo, const float *bias, const float *in_scale, const float *in_shift,
-                                             int in_relu_c0, float *y, float *stats, hoig_stream_t stream) {
+                                             int in_relu_c0, float *y, double *stats, hoig_stream_t stream) {
     if (!d || !x || !w_hi || !y || !in_scale || !in_shift || in_relu_c0 < 0) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     const InNorm in{in_scale, in_shift, in_relu_c0};

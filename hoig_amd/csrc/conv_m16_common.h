@@ -20,7 +20,7 @@ constexpr int round128(int v) { return (v + 127) / 128 * 128; }
 // hold different pixels (four xor steps), the WM waves with the same wn different rows (LDS, dead by now), then ONE atomic per
 // (workgroup, channel, moment) into the accumulators of the image.
 template <int NTW, int WM, int BN, int NT>
-__device__ __forceinline__ void m16_stats_epilogue(float (&st1)[NTW][4], float (&st2)[NTW][4], unsigned char *lds, float *stats_img, int N,
+__device__ __forceinline__ void m16_stats_epilogue(float (&st1)[NTW][4], float (&st2)[NTW][4], unsigned char *lds, double *stats, int b, int N,
                                                    int n0, int wm, int wn, int lane, int tid) {
     const int l15 = lane & 15, lg = lane >> 4;
 #pragma unroll
@@ -50,7 +50,7 @@ __device__ __forceinline__ void m16_stats_epilogue(float (&st1)[NTW][4], float (
         float v = 0.f;
 #pragma unroll
         for (int k = 0; k < WM; ++k) v += red[(k * 2 + mom) * BN + cl];
-        if (n0 + cl < N) atomicAdd(&stats_img[(size_t)mom * N + n0 + cl], v);
+        if (n0 + cl < N) hoig_stats_add(stats, b, N, mom, n0 + cl, v);
     }
 }
 

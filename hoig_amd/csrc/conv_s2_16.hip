@@ -335,7 +335,7 @@ __global__ __launch_bounds__(128 * WM) void conv_halo_s2_m16p_kernel(const HaloA
             }
         }
     }
-    if (p.stats) m16_stats_epilogue<NTW, WM, BN, NT>(st1, st2, smem, p.stats + (size_t)b * 2 * p.N, p.N, n0, wm, wn, lane, tid);
+    if (p.stats) m16_stats_epilogue<NTW, WM, BN, NT>(st1, st2, smem, p.stats, b, p.N, n0, wm, wn, lane, tid);
 }
 
 template <int BN, int WM>

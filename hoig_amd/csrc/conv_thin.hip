@@ -44,7 +44,7 @@ struct ThinArgs {
     int K, KP, N, NP;        // K = KS*KS*F (gemm reduction, padded to 16) ; N = the same count as wgrad's columns (padded to 32)
     int tiles_x, tiles_y, ntiles, strip;
     int HR, CW;              // halo image: rows, row pitch (elements)
-    float *stats;            // gemm forward (nullable): per image [sum | sum of squares][CD] of the stored values, added atomically
+    double *stats;            // gemm forward (nullable): per image [sum | sum of squares][CD] of the stored values, added atomically
 };
 
 template <bool FP16>
@@ -209,9 +209,8 @@ __global__ __launch_bounds__(NTHR) void thin_gemm_kernel(const ThinArgs p) {
             for (int j = 0; j < 2; ++j) {
                 const float s1 = st1[j] + __shfl_xor(st1[j], 32), s2 = st2[j] + __shfl_xor(st2[j], 32);
                 if (lh == 0) {
-                    float *dst = p.stats + (size_t)sb * 2 * p.CD + cbase + j * 32 + l31;
-                    atomicAdd(dst, s1);
-                    atomicAdd(dst + p.CD, s2);
+                    hoig_stats_add(p.stats, sb, p.CD, 0, cbase + j * 32 + l31, s1);
+                    hoig_stats_add(p.stats, sb, p.CD, 1, cbase + j * 32 + l31, s2);
                 }
                 st1[j] = st2[j] = 0.f;
             }
@@ -720,7 +719,7 @@ int launch_wgrad_t(const ThinArgs &a, int nt, int nd, dim3 grid, size_t smem, hi
 }  // namespace
 
 // forward of a thin-INPUT convolution (Ci <= 8, Co % 64 == 0); HOIG_EUNSUPPORTED otherwise
-int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st, float *stats) {
+int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st, double *stats) {
     if (d->precision == HOIG_PREC_F32 || !thin_geometry(d) || d->Ci > (d->R <= 3 ? 12 : 8) || d->Ci < 1 || (d->Co % 64)) return HOIG_EUNSUPPORTED;
     ThinArgs a;
     fill_common(a, d, d->Ci, d->Co);

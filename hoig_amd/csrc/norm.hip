@@ -22,7 +22,30 @@ inline int inorm_chunks(int HW) {
     return n;
 }
 
-// partial[b][chunk][0/1][c] = sum (v - pivot), sum (v - pivot)^2 over the chunk's rows; pivot = x[b][0][c]
+// The pivot of the shifted sums of (image b, channels c .. c+3): the median of three means of four pixels each, the twelve pixels
+// taken at the odd 24ths of the map.  A pivot k sigma from the channel's mean costs the variance about k^2 * 2^-24 of relative error,
+// so it has to be a typical value: a mean of four is within a sigma of the channel mean, and the median drops the one group that an
+// atypical pixel or block (pixel 0 is the zero-padded corner of the producing convolution) can spoil.  Only additions, a scale by a
+// power of two and min / max: every workgroup of the launch and the finalise kernel compute the same bits.
+__device__ __forceinline__ float4 inorm_pivot(const float *__restrict__ x, int b, int HW, int C, int c) {
+    float4 m[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = (int)(((int64_t)(2 * (4 * g + j) + 1) * HW) / 24);          // < HW
+            const float4 v = *reinterpret_cast<const float4 *>(x + ((size_t)b * HW + r) * C + c);
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        m[g] = make_float4(s.x * 0.25f, s.y * 0.25f, s.z * 0.25f, s.w * 0.25f);
+    }
+    auto med = [](float a, float b_, float c_) { return fmaxf(fminf(a, b_), fminf(fmaxf(a, b_), c_)); };
+    return make_float4(med(m[0].x, m[1].x, m[2].x), med(m[0].y, m[1].y, m[2].y), med(m[0].z, m[1].z, m[2].z),
+                       med(m[0].w, m[1].w, m[2].w));
+}
+
+// partial[b][chunk][0/1][c] = sum (v - pivot), sum (v - pivot)^2 over the chunk's rows; pivot = inorm_pivot
 // MODE_BWD: v = g' (sum) and g'*xhat (second sum), no pivot.
 template <bool BWD>
 __global__ __launch_bounds__(NT) void inorm_partial_kernel(const float *__restrict__ x, const float *__restrict__ mean,
@@ -44,7 +67,7 @@ __global__ __launch_bounds__(NT) void inorm_partial_kernel(const float *__restri
         float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
         float4 pv = make_float4(0, 0, 0, 0), mu = pv, rs = pv, sc = make_float4(1, 1, 1, 1), aw = sc, ab = pv;
         if (!BWD) {
-            pv = *reinterpret_cast<const float4 *>(x + (size_t)b * HW * C + c);
+            pv = inorm_pivot(x, b, HW, C, c);
         } else {
             mu = *reinterpret_cast<const float4 *>(mean + (size_t)b * C + c);
             rs = *reinterpret_cast<const float4 *>(rstd + (size_t)b * C + c);
@@ -103,7 +126,7 @@ __global__ __launch_bounds__(NT) void inorm_partial_kernel(const float *__restri
     (void)chunk;
 }
 
-// x == NULL: the sums are plain (pivot 0: they come from a convolution's epilogue, hoig_conv2d_fwd_packed_stats)
+// mean / rstd from the shifted sums of inorm_partial_kernel<false>
 __global__ void inorm_finalize_kernel(const float *__restrict__ x, float *__restrict__ partial, int HW, int C,
                                       int nchunks, float eps, float *__restrict__ mean, float *__restrict__ rstd,
                                       int total) {
@@ -116,10 +139,73 @@ __global__ void inorm_finalize_kernel(const float *__restrict__ x, float *__rest
     const float d = s1 * inv;
     float var = s2 * inv - d * d;
     var = var > 0.f ? var : 0.f;
-    mean[i] = (x ? x[(size_t)b * HW * C + c] : 0.f) + d;
+    const float4 pv = inorm_pivot(x, b, HW, C, c & ~3);
+    const float p = (c & 3) == 0 ? pv.x : (c & 3) == 1 ? pv.y : (c & 3) == 2 ? pv.z : pv.w;
+    mean[i] = p + d;
     rstd[i] = 1.f / sqrtf(var + eps);
     partial[(size_t)b * 2 * C + c] = 0.f;          // leave the accumulators zeroed for the next call (no memset launches)
     partial[(size_t)b * 2 * C + C + c] = 0.f;
+}
+
+// mean / rstd from the PLAIN sums a convolution's epilogue left (sum y, sum y^2 as fp64 accumulators [b][2][C]: hoig_stats_add in
+// common.h).  E[y^2] - E[y]^2 is taken in fp64, so what it loses is (1 + 3 (mean/sigma)^2) times the error of the SUMS -- the fp32
+// rounding of each workgroup's partial, about 1e-7 -- and it is only kept where E[y^2] <= SUMS_COND * var, i.e. |mean|/sigma < ~2.6.
+// Every other channel -- a near-constant one, a stem channel over a flat image -- is recomputed by this workgroup from y itself,
+// centred on the mean the sums gave: one workgroup per (image, four channels), which returns after reading its eight sums when none
+// of the four needs it.
+constexpr float SUMS_COND = 8.f;
+constexpr int RNT = 256;
+__global__ __launch_bounds__(RNT) void inorm_from_sums_kernel(const float *__restrict__ y, float *__restrict__ sums, int HW, int C,
+                                                              float eps, float *__restrict__ mean, float *__restrict__ rstd) {
+    const int b = blockIdx.y, c = blockIdx.x * 4;
+    double *acc = reinterpret_cast<double *>(sums) + (size_t)b * 2 * C + c;
+    const double invd = 1.0 / (double)HW;
+    const double m0 = acc[0] * invd, m1 = acc[1] * invd, m2_ = acc[2] * invd, m3 = acc[3] * invd;
+    const double q0 = acc[C] * invd, q1 = acc[C + 1] * invd, q2 = acc[C + 2] * invd, q3 = acc[C + 3] * invd;
+    const double v0 = q0 - m0 * m0, v1 = q1 - m1 * m1, v2 = q2 - m2_ * m2_, v3 = q3 - m3 * m3;
+    const bool redo = !(q0 <= SUMS_COND * v0) || !(q1 <= SUMS_COND * v1) || !(q2 <= SUMS_COND * v2) ||
+                      !(q3 <= SUMS_COND * v3);               // (uniform over the workgroup; an all-zero channel passes: 0 <= 0)
+    const float inv = 1.f / (float)HW;
+    float4 mu = make_float4((float)m0, (float)m1, (float)m2_, (float)m3);
+    float4 var = make_float4((float)v0, (float)v1, (float)v2, (float)v3);
+    if (redo) {
+        float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
+        for (int r = threadIdx.x; r < HW; r += RNT) {
+            const float4 v = *reinterpret_cast<const float4 *>(y + ((size_t)b * HW + r) * C + c);
+            const float dx = v.x - mu.x, dy = v.y - mu.y, dz = v.z - mu.z, dw = v.w - mu.w;
+            t1.x += dx; t1.y += dy; t1.z += dz; t1.w += dw;
+            t2.x += dx * dx; t2.y += dy * dy; t2.z += dz * dz; t2.w += dw * dw;
+        }
+        __shared__ float red[RNT / 64][8];
+        float t[8] = {t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o);
+        if ((threadIdx.x & 63) == 0)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) red[threadIdx.x >> 6][k] = t[k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                t[k] = 0.f;
+#pragma unroll
+                for (int w = 0; w < RNT / 64; ++w) t[k] += red[w][k];
+                t[k] *= inv;
+            }
+            var = make_float4(t[4] - t[0] * t[0], t[5] - t[1] * t[1], t[6] - t[2] * t[2], t[7] - t[3] * t[3]);
+            mu = make_float4(mu.x + t[0], mu.y + t[1], mu.z + t[2], mu.w + t[3]);
+        }
+    }
+    if (threadIdx.x == 0) {
+        *reinterpret_cast<float4 *>(mean + (size_t)b * C + c) = mu;
+        *reinterpret_cast<float4 *>(rstd + (size_t)b * C + c) =
+            make_float4(1.f / sqrtf(fmaxf(var.x, 0.f) + eps), 1.f / sqrtf(fmaxf(var.y, 0.f) + eps),
+                        1.f / sqrtf(fmaxf(var.z, 0.f) + eps), 1.f / sqrtf(fmaxf(var.w, 0.f) + eps));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = acc[C + k] = 0.0;   // leave the accumulators zeroed for the next call (only this workgroup reads these eight)
+    }
 }
 
 // sums[b][0/1][c] for the backward; affine grads accumulate atomically
@@ -284,13 +370,40 @@ __device__ __forceinline__ float4 tile_reduce(float4 v, float *red, int cq, int 
     __syncthreads();
     return o;
 }
+// two sums behind the same three barriers: red is 2 x [TPL][TCG] floats
+__device__ __forceinline__ void tile_reduce2(float4 &a, float4 &b, float *red, int cq, int pl) {
+    float *red2 = red + TPL * TCG;
+    *reinterpret_cast<float4 *>(red + pl * TCG + cq * 4) = a;
+    *reinterpret_cast<float4 *>(red2 + pl * TCG + cq * 4) = b;
+    __syncthreads();
+    float sa = 0.f, sb = 0.f;
+    const int c = threadIdx.x % TCG, part = threadIdx.x / TCG;
+#pragma unroll
+    for (int k = 0; k < TPL / (TNT / TCG); ++k) {
+        sa += red[(part * (TPL / (TNT / TCG)) + k) * TCG + c];
+        sb += red2[(part * (TPL / (TNT / TCG)) + k) * TCG + c];
+    }
+    __syncthreads();
+    red[part * TCG + c] = sa;
+    red2[part * TCG + c] = sb;
+    __syncthreads();
+    a = b = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < TNT / TCG; ++k) {
+        const float4 t = *reinterpret_cast<const float4 *>(red + k * TCG + cq * 4);
+        const float4 u = *reinterpret_cast<const float4 *>(red2 + k * TCG + cq * 4);
+        a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+        b.x += u.x; b.y += u.y; b.z += u.z; b.w += u.w;
+    }
+    __syncthreads();
+}
 
 __global__ __launch_bounds__(TNT) void inorm_tile_fwd_kernel(const float *__restrict__ x, int mode, const float *__restrict__ p0,
                                                              const float *__restrict__ p1, int ldp, int act, float slope,
                                                              const float *__restrict__ residual, float eps,
                                                              float *__restrict__ y, float *__restrict__ mean,
                                                              float *__restrict__ rstd, int HW, int C) {
-    __shared__ float red[TPL * TCG];
+    __shared__ float red[2 * TPL * TCG];
     const int b = blockIdx.y, c0 = blockIdx.x * TCG;
     const int cq = threadIdx.x % (TCG / 4), pl = threadIdx.x / (TCG / 4), c = c0 + cq * 4;
     const size_t base = (size_t)b * HW * C + c;
@@ -304,17 +417,23 @@ __global__ __launch_bounds__(TNT) void inorm_tile_fwd_kernel(const float *__rest
     }
     s = tile_reduce(s, red, cq, pl);
     const float inv = 1.f / (float)HW;
-    const float4 mu = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 mu = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+    // second pass, centred on the first pass's mean -- whose own rounding (16 sequential additions per lane at the channel's LEVEL)
+    // is |mean| / sigma * 2^-24 in units of sigma: the sum of the centred values measures it, and corrects mean and variance
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f), e = q;
 #pragma unroll
     for (int k = 0; k < TEPT; ++k)
         if (pl + k * TPL < HW) {
             const float dx = v[k].x - mu.x, dy = v[k].y - mu.y, dz = v[k].z - mu.z, dw = v[k].w - mu.w;
+            e.x += dx; e.y += dy; e.z += dz; e.w += dw;
             q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
         }
-    q = tile_reduce(q, red, cq, pl);
-    const float4 rs = make_float4(1.f / sqrtf(q.x * inv + eps), 1.f / sqrtf(q.y * inv + eps), 1.f / sqrtf(q.z * inv + eps),
-                                  1.f / sqrtf(q.w * inv + eps));
+    tile_reduce2(q, e, red, cq, pl);
+    e = make_float4(e.x * inv, e.y * inv, e.z * inv, e.w * inv);
+    mu = make_float4(mu.x + e.x, mu.y + e.y, mu.z + e.z, mu.w + e.w);
+    q = make_float4(fmaxf(q.x * inv - e.x * e.x, 0.f), fmaxf(q.y * inv - e.y * e.y, 0.f), fmaxf(q.z * inv - e.z * e.z, 0.f),
+                    fmaxf(q.w * inv - e.w * e.w, 0.f));
+    const float4 rs = make_float4(1.f / sqrtf(q.x + eps), 1.f / sqrtf(q.y + eps), 1.f / sqrtf(q.z + eps), 1.f / sqrtf(q.w + eps));
     if (pl == 0) {
         *reinterpret_cast<float4 *>(mean + (size_t)b * C + c) = mu;
         *reinterpret_cast<float4 *>(rstd + (size_t)b * C + c) = rs;
@@ -354,7 +473,7 @@ __global__ __launch_bounds__(TNT) void inorm_tile_bwd_kernel(const float *__rest
                                                              int act, float slope, float *__restrict__ dx,
                                                              float *__restrict__ dp0, float *__restrict__ dp1, int HW, int C,
                                                              const float *__restrict__ addend, int split) {
-    __shared__ float red[TPL * TCG];
+    __shared__ float red[2 * TPL * TCG];
     const int b = blockIdx.y, c0 = blockIdx.x * TCG;
     const int cq = threadIdx.x % (TCG / 4), pl = threadIdx.x / (TCG / 4), c = c0 + cq * 4;
     const size_t base = (size_t)b * HW * C + c;
@@ -404,8 +523,7 @@ __global__ __launch_bounds__(TNT) void inorm_tile_bwd_kernel(const float *__rest
         s1.x += gg.x; s1.y += gg.y; s1.z += gg.z; s1.w += gg.w;
         s2.x += gg.x * hh.x; s2.y += gg.y * hh.y; s2.z += gg.z * hh.z; s2.w += gg.w * hh.w;
     }
-    s1 = tile_reduce(s1, red, cq, pl);
-    s2 = tile_reduce(s2, red, cq, pl);
+    tile_reduce2(s1, s2, red, cq, pl);
     if (mode == 1 && pl == 0) {             // affine parameter gradients: dbias += sum g, dweight += sum g*xhat (g before * weight)
         if (dp1) { atomicAdd(dp1 + c, s1.x); atomicAdd(dp1 + c + 1, s1.y); atomicAdd(dp1 + c + 2, s1.z); atomicAdd(dp1 + c + 3, s1.w); }
         if (dp0) { atomicAdd(dp0 + c, s2.x); atomicAdd(dp0 + c + 1, s2.y); atomicAdd(dp0 + c + 2, s2.z); atomicAdd(dp0 + c + 3, s2.w); }
@@ -464,13 +582,11 @@ extern "C" int64_t hoig_inorm_workspace_bytes(int B, int HW, int C) {
     return (ACC_POOL + (int64_t)B * 2 * C) * (int64_t)sizeof(float);
 }
 
-extern "C" int hoig_inorm_stats_from_sums(int B, int HW, int C, float eps, float *mean, float *rstd, void *workspace,
+extern "C" int hoig_inorm_stats_from_sums(const float *y, int B, int HW, int C, float eps, float *mean, float *rstd, void *workspace,
                                           hoig_stream_t stream) {
-    if (!mean || !rstd || !workspace) return HOIG_EINVAL;
-    if (B <= 0 || HW <= 0 || C <= 0 || (int64_t)B * 2 * C > ACC_POOL) return HOIG_EUNSUPPORTED;
-    const int total = B * C;
-    inorm_finalize_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(nullptr, (float *)workspace, HW, C, 0, eps, mean,
-                                                                                rstd, total);
+    if (!y || !mean || !rstd || !workspace) return HOIG_EINVAL;
+    if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || B > 65535 || (int64_t)B * 4 * C > ACC_POOL) return HOIG_EUNSUPPORTED;   // (fp64 sums)
+    inorm_from_sums_kernel<<<dim3(C / 4, B), RNT, 0, (hipStream_t)stream>>>(y, (float *)workspace, HW, C, eps, mean, rstd);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

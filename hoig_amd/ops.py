@@ -966,7 +966,7 @@ def conv2d_after_norm(xraw, gamma, beta, w, b=None, first=None, norm_next=False,
     rstd = torch.empty_like(mean)
     ws, have = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, dev, take=(xraw.data_ptr(), B, HW, C))
     if have:
-        call('hoig_inorm_stats_from_sums', B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
+        call('hoig_inorm_stats_from_sums', _p(xraw), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
     else:
         call('hoig_inorm_stats', _p(xraw), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
     Cg = C1 + C

@@ -31,7 +31,7 @@ def _norm_workspace(nfloats, device, take=None):
         ws = torch.zeros(max(nfloats, 1 << 20), dtype=torch.float32, device=device)
         _norm_ws[key] = ws
     elif pend is not None:
-        ws[:pend[1] * 2 * pend[3]].zero_()
+        ws[:pend[1] * 4 * pend[3]].zero_()          # (the convolutions' sums are fp64: two floats each)
     return (ws, False) if take is not None else ws
 
 
@@ -54,7 +54,7 @@ def _conv_stats_workspace(y):
     """Accumulators for the statistics of `y` (a convolution output about to be written), or None when its instance norm would
     not read them: maps of <= 1024 pixels take the one-launch norm kernel, which computes its own (but see small_map_sums)."""
     B, H, W_, C = y.shape
-    if (H * W_ <= 1024 and not _small_sums[0]) or C % 4 or B * 2 * C > (1 << 18):        # (1 << 18: the accumulator pool, norm.hip ACC_POOL)
+    if (H * W_ <= 1024 and not _small_sums[0]) or C % 4 or B * 4 * C > (1 << 18):        # (1 << 18: the accumulator pool, norm.hip ACC_POOL; the sums are fp64)
         return None
     return _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, H * W_, C) // 4, y.device)
 
@@ -90,7 +90,7 @@ class _INorm(Function):
         if rc == L.EUNSUPPORTED:
             ws, have = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device, take=(x.data_ptr(), B, HW, C))
             if have:              # the convolution that made x left its sums in the accumulators: no pass over x for them
-                call('hoig_inorm_stats_from_sums', B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
+                call('hoig_inorm_stats_from_sums', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
             else:
                 call('hoig_inorm_stats', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
             call('hoig_inorm_apply', _o._p(x), _o._p(mean), _o._p(rstd), mode, _o._p(p0), _o._p(p1), act, slope, _o._p(residual), _o._p(y),
@@ -164,7 +164,7 @@ class _SpadeFused(Function):
         if rc == L.EUNSUPPORTED:
             ws, have = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device, take=(x.data_ptr(), B, HW, C))
             if have:
-                call('hoig_inorm_stats_from_sums', B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
+                call('hoig_inorm_stats_from_sums', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
             else:
                 call('hoig_inorm_stats', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
             call('hoig_inorm_apply_ld', _o._p(x), _o._p(mean), _o._p(rstd), 2, _o._p(gb), gb.data_ptr() + 4 * C, 2 * C, act, slope, None,

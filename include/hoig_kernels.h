@@ -115,7 +115,7 @@ int hoig_inorm_fold(const float *mean, const float *rstd, const float *gamma /*n
                     float *scale, float *shift, int ld_out, hoig_stream_t stream);
 int hoig_conv2d_fwd_packed_normin(const hoig_conv_desc *d, const float *x, int C1, const float *x2 /*nullable*/, const uint16_t *w_hi,
                                   const uint16_t *w_lo, const float *bias /*nullable*/, const float *in_scale, const float *in_shift,
-                                  int in_relu_c0, float *y, float *stats /*nullable*/, hoig_stream_t stream);
+                                  int in_relu_c0, float *y, double *stats /*nullable*/, hoig_stream_t stream);
 int hoig_conv2d_bwd_weight_split(const hoig_conv_desc *d, const float *x, const uint16_t *dy_split, float *dw, hoig_stream_t stream);
 /* dx = data gradient (+ addend when non-null: hoig_conv2d_bwd_data_packed_add) of a stride-1 "same" 3x3 Conv2d from pre-split dy, on the
  * 8-row tilings of the v_mfma_f32_16x16x32 kernel (Hi % 8 == 0, Wi % 32 == 0 and enough tiles: HOIG_EUNSUPPORTED otherwise -- the
@@ -169,20 +169,22 @@ int hoig_conv2d_fwd_packed(const hoig_conv_desc *d, const float *x, const uint16
 int hoig_conv2d_bwd_data_packed(const hoig_conv_desc *d, const float *dy, const uint16_t *wt_hi, const uint16_t *wt_lo,
                                 float *dx, hoig_stream_t stream);
 /* y = conv(x) AND, from the same epilogue, the statistics of the instance norm that reads y next (generator.py:16-22 conv -> IN ->
- * ReLU): stats[b][0][co] += sum of y over image b, stats[b][1][co] += sum of y*y (fp32 atomics, one per workgroup and
- * channel; stats = the accumulators of an instance-norm workspace, zero on entry), consumed by hoig_inorm_stats_from_sums instead of
+ * ReLU): stats[b][0][co] += sum of y over image b, stats[b][1][co] += sum of y*y -- DOUBLES, B * 2 * Co of them, in
+ * every entry point that takes `stats` (fp64
+ * atomics, one per workgroup and channel, of the workgroup's fp32 partial; stats = the accumulators of an instance-norm workspace,
+ * zero on entry: B * 4 * Co <= 2^18 floats of its pool), consumed by hoig_inorm_stats_from_sums instead of
  * a pass over y.  HOIG_EUNSUPPORTED where the layer's kernel has no such epilogue (it exists on the 3x3 stride-1 "same" and the 3x3
  * stride-2 halo kernels, Conv2d and ConvTranspose2d): the caller then runs the plain convolution and hoig_inorm_stats. */
 int hoig_conv2d_fwd_packed_stats(const hoig_conv_desc *d, const float *x, const uint16_t *w_hi, const uint16_t *w_lo,
-                                 const float *bias /*nullable*/, float *y, float *stats, hoig_stream_t stream);
+                                 const float *bias /*nullable*/, float *y, double *stats, hoig_stream_t stream);
 int hoig_conv2d_cat_fwd_packed_stats(const hoig_conv_desc *d, const float *x1, int C1, const float *x2, const uint16_t *w_hi,
-                                     const uint16_t *w_lo, const float *bias /*nullable*/, float *y, float *stats,
+                                     const uint16_t *w_lo, const float *bias /*nullable*/, float *y, double *stats,
                                      hoig_stream_t stream);
 /* The same for the layers the packed kernels do not take: hoig_conv2d_fwd (unpacked weights) with the sums, HOIG_EUNSUPPORTED unless
  * the layer is a thin-INPUT convolution on the MFMA path (Ci <= 8 (12 for 3x3), Co % 64 == 0, odd square stride-1 "same" kernel,
  * Hi % 4 == 0, Wi % 32 == 0, a 16-bit precision): the generator's 7x7 stems (generator.py:100,262), whose output is the largest
  * tensor an instance norm's statistics pass would re-read. */
-int hoig_conv2d_fwd_stats(const hoig_conv_desc *d, const float *x, const float *w, const float *bias /*nullable*/, float *y, float *stats,
+int hoig_conv2d_fwd_stats(const hoig_conv_desc *d, const float *x, const float *w, const float *bias /*nullable*/, float *y, double *stats,
                           hoig_stream_t stream);
 /* dx = data gradient + addend (addend: the gradient that reaches the same tensor through its OTHER consumer, e.g. the skip path of
  * a residual block, generator.py:29-32 `x + self.main(x)`; torch's autograd engine sums the two in a separate pass).  Returns
@@ -214,7 +216,7 @@ int hoig_conv2d_cat_fwd_f6(const hoig_conv_desc *d, const float *x1, int C1, con
  * Same HOIG_EUNSUPPORTED conditions as hoig_conv2d_fwd_f6. */
 int hoig_conv2d_fwd_f6_ex(const hoig_conv_desc *d, const float *x, int C1, const float *x2 /*nullable*/, const uint16_t *w_hi,
                           const uint8_t *q_hi, const uint8_t *q_lo, const float *bias /*nullable*/, const float *in_scale /*nullable*/,
-                          const float *in_shift /*nullable*/, int in_relu_c0, float *y, float *stats /*nullable*/, hoig_stream_t stream);
+                          const float *in_shift /*nullable*/, int in_relu_c0, float *y, double *stats /*nullable*/, hoig_stream_t stream);
 /* all eligible weights of a flat parameter buffer in one launch: rows = int64[nrows][6] = (offset of the weight in `flat`, Co,
  * RS, Ci, byte offset of its records in q_hi / q_lo (a multiple of 4), index of its first task); a task = one (output channel,
  * tap, 32 input channels) half record: Co*RS*Ci/32 per weight */
@@ -251,10 +253,15 @@ int hoig_inorm_apply(const float *x, const float *mean, const float *rstd, int m
                      hoig_stream_t stream);
 /* same with gamma/beta rows `ld_p` floats apart (mode 2 only): lets gamma and beta live side by side in ONE [.,2C] tensor
  * (the output of the fused gamma|beta convolution), p0 = gb, p1 = gb + C, ld_p = 2C */
-/* mean / rstd from sums that a convolution's epilogue left in the workspace's accumulators (hoig_conv2d_fwd_packed_stats; plain
- * sums: var = E[y^2] - E[y]^2 in fp32, adequate for the outputs of convolutions over normalised activations this is used for);
- * leaves the accumulators zero like hoig_inorm_stats */
-int hoig_inorm_stats_from_sums(int B, int HW, int C, float eps, float *mean, float *rstd, void *workspace, hoig_stream_t stream);
+/* mean / rstd of y from the sums that the convolution which wrote y left in the workspace's accumulators (hoig_conv2d_fwd_packed_stats
+ * and its kin: PLAIN sums in fp64).  var = E[y^2] - E[y]^2, taken in fp64, is kept only for the channels where it is well conditioned
+ * (E[y^2] <= 8 var, |mean|/sigma below ~2.6); every other (image, channel) -- a near-constant channel, a stem channel over a flat
+ * image -- is recomputed in the same launch from y, centred on the mean the sums gave, so the result holds the bound of the two-pass
+ * kernels for any input (tests/test_norm_gpu.py; figures in docs/norm_conditioning.md).  C % 4 == 0 and B * 4 * C <= 2^18,
+ * HOIG_EUNSUPPORTED otherwise; leaves the accumulators zero like hoig_inorm_stats, whose shifted sums take their pivot from a median
+ * of means of twelve pixels spread over the map. */
+int hoig_inorm_stats_from_sums(const float *y, int B, int HW, int C, float eps, float *mean, float *rstd, void *workspace,
+                               hoig_stream_t stream);
 int hoig_inorm_apply_ld(const float *x, const float *mean, const float *rstd, int mode, const float *p0, const float *p1,
                         int ld_p, int act, float slope, const float *residual /*nullable*/, float *y, int B, int HW, int C,
                         hoig_stream_t stream);

@@ -400,7 +400,7 @@ def test_inference_norm_applied_by_the_f6_loader_and_sums_left_by_its_epilogue(c
         _p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         a, a2 = (first, xn) if first is not None else (xn, None)
         y0 = torch.empty_like(y)
-        sums = torch.zeros(B, 2, Co, device='cuda')
+        sums = torch.zeros(B, 2, Co, dtype=torch.float64, device='cuda')          # (the epilogues accumulate in fp64)
         assert L.lib.hoig_conv2d_fwd_f6_ex(ctypes.byref(d), _p(a), C1, _p(a2), _p(hi), _p(qh), _p(ql), _p(bias), None, None, 0, _p(y0), _p(sums),
                                            st) == L.OK
         torch.cuda.synchronize()
@@ -443,7 +443,7 @@ def test_stem_convolution_leaves_channel_sums_for_its_norm(Ci, B):
         st = torch.cuda.current_stream().cuda_stream
         _p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         y0, y1 = torch.empty(B, H, W, 64, device='cuda'), torch.empty(B, H, W, 64, device='cuda')
-        sums = torch.zeros(B, 2, 64, device='cuda')
+        sums = torch.zeros(B, 2, 64, dtype=torch.float64, device='cuda')          # (the epilogues accumulate in fp64)
         L.call('hoig_conv2d_fwd', ctypes.byref(d), _p(x), _p(w), _p(bias), _p(y0), st)
         assert L.lib.hoig_conv2d_fwd_stats(ctypes.byref(d), _p(x), _p(w), _p(bias), _p(y1), _p(sums), st) == L.OK
         torch.cuda.synchronize()

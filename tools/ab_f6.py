@@ -22,7 +22,7 @@ for B, Ci, Co, H, W in SHAPES:
     w = ops.pack_weight(torch.randn(Co, Ci, 3, 3, device='cuda') * 0.02)
     y = torch.empty(B, H, W, Co, device='cuda')
     sc, sh = torch.rand(B, Ci, device='cuda') + 0.5, torch.randn(B, Ci, device='cuda')
-    sums = torch.zeros(B, 2, Co, device='cuda')
+    sums = torch.zeros(B, 2, Co, dtype=torch.float64, device='cuda')
     d3 = L.ConvDesc(B, H, W, Ci, H, W, Co, 3, 3, 1, 1, 0, 0, 0.0, L.PREC_BF16X3)
     d6 = L.ConvDesc(B, H, W, Ci, H, W, Co, 3, 3, 1, 1, 0, 0, 0.0, L.PREC_F16F6)
     hi, lo = ops._packed_planes(w, False, False)
