@@ -153,6 +153,9 @@ _SIGS = {
     'hoig_global_avgpool': [_vp, _vp, _i, _i, _i, _vp],
     'hoig_lpips_layer': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     'hoig_ssim': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _f, _vp, _vp],
+    'hoig_jpeg_entropy_host': [_vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _vp],
+    'hoig_jpeg_decode_bgr_u8': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp],
+    'hoig_jpeg_reconstruct_bgr_u8': [_vp, _vp, _i, _vp, _i64, _vp, _i64, _vp],
 }
 
 
@@ -188,6 +191,8 @@ def _load():
     lib.hoig_lpips_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_ssim_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
     lib.hoig_ssim_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
+    lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_version.argtypes = []
     lib.hoig_version.restype = ctypes.c_char_p
     return lib

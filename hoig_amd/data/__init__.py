@@ -7,7 +7,8 @@ on the host and re-parse the object mesh text for every item (hov3_dataset.py:21
 the annotation; the batch of 8-bit frames goes to the GPU from pinned memory and ``DeviceStage`` (device_stage.py) does the rest there
 in a handful of launches -- the reference's arithmetic, integer for integer (hoig_amd/csrc/data_prep.hip) -- with the object meshes
 parsed once and kept on the device.  ``load_data()`` yields the reference's batch dict with device tensors; ``Trainer.set_input``
-takes it as it is."""
+takes it as it is.  With ``opt.device_jpeg`` (or HOIG_DEVICE_JPEG=1; default off) a worker does not decode a JPEG frame either: it
+reads the file and parses its headers (jpeg.py), and the device stage decodes the batch's files (hoig_amd/csrc/jpeg.hip)."""
 import torch.utils.data
 
 from .device_stage import DeviceStage, collate_raw

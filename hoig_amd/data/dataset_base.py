@@ -5,6 +5,7 @@ import os
 import pickle
 
 import numpy as np
+import torch
 import torch.utils.data
 
 
@@ -17,6 +18,25 @@ def read_pickle(path, what='file'):
         except UnicodeDecodeError:
             f.seek(0)
             return pickle.load(f)
+
+
+def device_jpeg_enabled(opt):
+    """``opt.device_jpeg`` or HOIG_DEVICE_JPEG=1: JPEG frames leave the worker as file bytes and are decoded on the device."""
+    return bool(getattr(opt, 'device_jpeg', False)) or os.environ.get('HOIG_DEVICE_JPEG', '') == '1'
+
+
+def frame_entries(path, device_jpeg, imread):
+    """The frame part of a raw sample: ``{'frame': decoded BGR uint8}`` -- or, with the option on and a .jpg / .jpeg file the device
+    decoder takes (``jpeg.parse`` gives a plan), ``{'jpeg': the file's bytes, 'jpeg_plan': the plan}``: the worker then only reads."""
+    if device_jpeg and path.lower().endswith(('.jpg', '.jpeg')):
+        from . import jpeg as J                         # (only with the option on: a worker's imports do not change otherwise)
+        with open(path, 'rb') as f:
+            data = f.read()
+        plan = J.parse(data)
+        if plan is not None:
+            plan['path'] = path
+            return {'jpeg': torch.frombuffer(bytearray(data), dtype=torch.uint8), 'jpeg_plan': plan}
+    return {'frame': torch.from_numpy(imread(path))}
 
 
 class PairIndex(object):
@@ -54,6 +74,7 @@ class DatasetBase(torch.utils.data.Dataset):
     def __init__(self, opt, is_for_train):
         super(DatasetBase, self).__init__()
         self._opt, self._is_for_train = opt, is_for_train
+        self._device_jpeg = device_jpeg_enabled(opt)
         self._index = None
 
     @property

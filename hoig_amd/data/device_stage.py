@@ -17,12 +17,34 @@ PATCH = 256
 MASK_SIZE = (640, 480)              # cv2.resize(mask, (640, 480)): (width, height)
 
 
+_JPEG_KEYS = ('frame', 'jpeg', 'jpeg_plan')
+
+
+def _collate_jpeg(recs):
+    """The frame part of a view whose records carry JPEG files (opt.device_jpeg): 'jpeg' = the files packed into ONE byte buffer with
+    their plan records and interval offsets (jpeg.pack: what hoig_jpeg_decode_bgr_u8 takes; one pinned buffer, one H2D copy), the
+    batch slot, path and size of each; 'frame' = per sample the decoded frame of a record that has one (a PNG, a progressive file),
+    else None.  Image i decodes into slot i of the batch's [B][Hs][Ws][3] buffer."""
+    from . import jpeg as J
+    slots = [i for i, r in enumerate(recs) if 'jpeg' in r]
+    plans = [recs[i]['jpeg_plan'] for i in slots]
+    offsets = [i * p['height'] * p['width'] * 3 for i, p in zip(slots, plans)]
+    data, records, intervals = J.pack([(recs[i]['jpeg'].numpy(), p) for i, p in zip(slots, plans)], offsets)
+    return {'frame': [r.get('frame') for r in recs],
+            'jpeg': {'bytes': torch.from_numpy(data), 'plans': torch.from_numpy(records.view(np.uint8).reshape(-1)),
+                     'intervals': torch.from_numpy(intervals), 'slots': slots, 'paths': [p['path'] for p in plans],
+                     'sizes': [(p['height'], p['width']) for p in plans]}}
+
+
 def collate_raw(items):
     """Stack the per-sample records of a batch key by key (tensors -> one tensor, everything else -> a list)."""
     out = {}
     for side in ('A', 'B'):
         recs = [it[side] for it in items]
         col = {}
+        if any('jpeg' in r for r in recs):
+            col.update(_collate_jpeg(recs))
+            recs = [{k: v for k, v in r.items() if k not in _JPEG_KEYS} for r in recs]
         for k in recs[0]:
             vals = [r[k] for r in recs]
             same = torch.is_tensor(vals[0]) and all(v.shape == vals[0].shape for v in vals)
@@ -62,19 +84,29 @@ class DeviceStage(object):
         self._meshes = MeshCache(dataset, self.device)
         self._max_verts = dataset.max_obj_verts
         self._stream = None
+        self._decodes = []                              # (event, pinned status words, paths) of the JPEG decodes of the batch being issued
 
     # ---- one view (A or B) of a batch
     def _images(self, col):
         L, dev = self._L, self.device
-        frames, masks = col['frame'], col.get('mask')
-        if not torch.is_tensor(frames) or not (masks is None or torch.is_tensor(masks)):
+        frames, masks, files = col['frame'], col.get('mask'), col.get('jpeg')
+        sizes = set(tuple(hw) for hw in files['sizes']) | set(tuple(f.shape[:2]) for f in frames if f is not None) if files else ()
+        if not (torch.is_tensor(frames) or len(sizes) == 1) or not (masks is None or torch.is_tensor(masks)):
             raise ValueError('the frames (and the masks) of a batch must have one size')
-        B, Hs, Ws, _ = frames.shape
         st = torch.cuda.current_stream().cuda_stream
         p = lambda t: ctypes.c_void_p(t.data_ptr())
+        if files:                                       # opt.device_jpeg: the workers sent files, not pixels
+            (Hs, Ws), B = next(iter(sizes)), len(frames)
+            f_dev = torch.empty((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+            for i, f in enumerate(frames):              # (the records the host decoded: not a JPEG, or not one the device takes)
+                if f is not None:
+                    f_dev[i].copy_(f, non_blocking=True)
+            self._decode_jpeg(files, f_dev)
+        else:
+            B, Hs, Ws, _ = frames.shape
+            f_dev = frames.to(dev, non_blocking=True)
         trans = np.stack([G.patch_transform(b) for b in col['bbox'].numpy()])                   # (B, 2, 3) float32, host
         m_dev = torch.from_numpy(trans.astype(np.float64).reshape(B, 6)).to(dev, non_blocking=True)
-        f_dev = frames.to(dev, non_blocking=True)
         image = torch.empty((B, 3, PATCH, PATCH), dtype=torch.float32, device=dev)
         L.call('hoig_warp_affine_u8', p(f_dev), B, Hs, Ws, 3, p(m_dev), PATCH, PATCH, 1, p(image), st)
         if masks is None:                                                   # (the DexYCB copy has no arm mask)
@@ -85,6 +117,28 @@ class DeviceStage(object):
         mask = torch.empty((B, 1, PATCH, PATCH), dtype=torch.float32, device=dev)
         L.call('hoig_warp_affine_u8', p(big), B, MASK_SIZE[1], MASK_SIZE[0], 3, p(m_dev), PATCH, PATCH, 2, p(mask), st)
         return image, mask, torch.from_numpy(trans)
+
+    def _decode_jpeg(self, files, out):
+        """hoig_jpeg_decode_bgr_u8 on the packed files of a view, into their slots of ``out``; the status words go back through pinned
+        memory behind an event of their own, for ``finish`` to read."""
+        L, dev = self._L, self.device
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        plans = files['plans']
+        n = len(files['slots'])
+        work_bytes = L.lib.hoig_jpeg_decode_workspace_bytes(p(plans), n)        # (writes the workspace offsets into the host records)
+        if work_bytes < 0:
+            raise ValueError('a JPEG plan outside the supported set: %s' % files['paths'])
+        data, plans_dev = files['bytes'].to(dev, non_blocking=True), plans.to(dev, non_blocking=True)
+        intervals = files['intervals'].to(dev, non_blocking=True)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        L.call('hoig_jpeg_decode_bgr_u8', p(data), data.numel(), p(plans), p(plans_dev), n, p(intervals), intervals.numel(), p(out),
+               out.numel(), p(status), p(work), work_bytes, torch.cuda.current_stream().cuda_stream)
+        back = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        back.copy_(status, non_blocking=True)
+        decoded = torch.cuda.Event()
+        decoded.record()
+        self._decodes.append((decoded, back, files['paths']))
 
     def _object_vertices(self, col):
         """hov3_dataset.py:246-248: zeros((7866, 3), float32); [:n] = v @ Rodrigues(objRot).T + objTrans; ycb_dataset.py:165-169,292-293:
@@ -125,6 +179,7 @@ class DeviceStage(object):
         if self._stream is None:
             from .. import ops
             self._stream = ops.new_stream(self.device, 'loader')
+        self._decodes = []
         with torch.cuda.stream(self._stream):
             a, b = self._view(raw['A']), self._view(raw['B'])
             batch = {'imageA': a[0], 'maskA': a[1], 'manoA': a[2], 'nameA': a[3],
@@ -135,15 +190,25 @@ class DeviceStage(object):
                 batch.update(self._prepare(batch))
             done = torch.cuda.Event()
             done.record()
-        return batch, done, raw                                         # (raw: the pinned source stays alive until the copies ran)
+        return batch, done, (raw, self._decodes)                        # (raw: the pinned source stays alive until the copies ran)
 
     def finish(self, pending):
-        batch, done, _ = pending
+        batch, done, (_, decodes) = pending
+        for decoded, status, paths in decodes:          # opt.device_jpeg: a file the device could not decode is an error HERE
+            decoded.synchronize()
+            bad = ['%s (%s)' % (path, self._jpeg_status(word)) for path, word in zip(paths, status.tolist()) if word]
+            if bad:
+                raise OSError('cannot decode the JPEG data of ' + ', '.join(bad))
         cur = torch.cuda.current_stream()
         cur.wait_event(done)
         for t in self._tensors(batch):
             t.record_stream(cur)
         return batch
+
+    @staticmethod
+    def _jpeg_status(word):
+        from . import jpeg as J
+        return J.status_text(word)
 
     @staticmethod
     def _tensors(batch):

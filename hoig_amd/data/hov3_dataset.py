@@ -9,7 +9,7 @@ import os
 import numpy as np
 import torch
 
-from .dataset_base import DatasetBase, PairIndex, read_pickle
+from .dataset_base import DatasetBase, PairIndex, frame_entries, read_pickle
 
 OBJNAMES = ['003_cracker_box', '004_sugar_box', '006_mustard_bottle', '010_potted_meat_can', '011_banana', '021_bleach_cleanser',
             '025_mug', '035_power_drill', '037_scissors']                      # object id = position in this list (hov3_dataset.py:13)
@@ -64,7 +64,7 @@ class HOv3Dataset(DatasetBase):
         f32 = lambda key: torch.from_numpy(np.asarray(anno[key]).astype(np.float32))
         f64 = lambda key: torch.from_numpy(np.asarray(anno[key], dtype=np.float64).reshape(3))
         return {
-            'frame': torch.from_numpy(imread_bgr(os.path.join(base, 'rgb', frame))),
+            **frame_entries(os.path.join(base, 'rgb', frame), self._device_jpeg, imread_bgr),
             'mask': torch.from_numpy(imread_bgr(os.path.join(base, 'mask', '%05d.png' % int(stem)))),
             'bbox': torch.as_tensor(np.asarray(self._bbox_of_video[video], dtype=np.float64)),
             'cam': f32('camMat'), 'pose': f32('handPose'), 'shape': f32('handBeta'), 'handtrans': f32('handTrans'),

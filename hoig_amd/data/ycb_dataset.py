@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 
-from .dataset_base import DatasetBase, PairIndex, read_pickle
+from .dataset_base import DatasetBase, PairIndex, frame_entries, read_pickle
 from .hov3_dataset import imread_bgr
 
 OBJNAMES = ['002_master_chef_can', '003_cracker_box', '004_sugar_box', '005_tomato_soup_can', '006_mustard_bottle',
@@ -51,7 +51,7 @@ class YCBDataset(DatasetBase):
         pose[:3] = posed[grasp]                                                  # float32 values, widened: the device works in float64
         k = info['intrinsics']
         return {
-            'frame': torch.from_numpy(imread_bgr(os.path.join(self._pics, video, 'color_%06d.jpg' % frame))),
+            **frame_entries(os.path.join(self._pics, video, 'color_%06d.jpg' % frame), self._device_jpeg, imread_bgr),
             'bbox': torch.tensor([x0, y0, x1 - x0, y1 - y0], dtype=torch.float64),
             'cam': torch.tensor([k['fx'], k['fy'], k['ppx'], k['ppy']], dtype=torch.float32),
             'pose': torch.from_numpy(label['pose_m'])[0].float(),

@@ -641,6 +641,53 @@ int64_t hoig_ssim_workspace_bytes(int B, int H, int W, int C, int win);
 int hoig_ssim(const float *x, const float *y, float *ssim_out, float *cs_out, int B, int H, int W, int C, float data_range, float K1,
               float K2, int win, float sigma, void *workspace, hoig_stream_t stream);
 
+/* ---- JPEG FRAMES DECODED ON THE DEVICE (hoig_amd/csrc/jpeg.hip, jpeg_entropy.h, jpeg_host.cpp; hoig_amd/data/jpeg.py parses the
+ *      headers on the host).  Baseline and extended-sequential Huffman, 8-bit, one interleaved scan; 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2)
+ *      and single-component files.  The result is what Pillow on libjpeg-turbo gives, byte for byte: jidctint's islow IDCT, fancy
+ *      upsampling, libjpeg's fixed-point YCbCr -> RGB -- as interleaved BGR uint8 [H][W][3], cv2.imread's layout
+ *      and hoig_warp_affine_u8's input.
+ *      Three launches per batch: entropy decode (one wave per image and restart interval; serial inside an interval) -> int16
+ *      coefficients; dequantise + IDCT -> padded uint8 component planes; upsample + colour conversion -> BGR. ---- */
+enum { HOIG_JPEG_ECODE = 1,     /* no Huffman code matches, a run leaves the block, or a table is not a prefix code */
+       HOIG_JPEG_EOVERRUN = 2,  /* the interval's blocks need more bits than it holds (a truncated file) */
+       HOIG_JPEG_EMARKER = 4,   /* a restart marker is missing, out of order, or an interval's offsets are not inside the data */
+       HOIG_JPEG_ETRAILING = 8  /* whole bytes are left in an interval after its last block */ };
+/* One image of a batch.  The caller fills everything above `coef_off`; hoig_jpeg_decode_workspace_bytes fills the two offsets. */
+typedef struct hoig_jpeg_plan {
+    int64_t data_off;          /* first byte of the scan's entropy-coded data in the packed byte buffer */
+    int64_t out_off;           /* first byte of this image's [height][width][3] result in the output buffer */
+    int64_t coef_off;          /* workspace: int16 coefficients, [component][block row][block column][64] of the padded planes */
+    int64_t plane_off;         /* workspace: uint8 planes, [component][8 x block rows][8 x block columns] */
+    int32_t data_len;          /* bytes of entropy-coded data (up to the marker that ends the scan) */
+    int32_t width, height;
+    int32_t ncomp;             /* 1 or 3 (Y, Cb, Cr; the chroma components are sampled 1 x 1) */
+    int32_t hs, vs;            /* sampling factors of the first component: 1x1, 2x1 or 2x2 */
+    int32_t restart_interval;  /* MCUs per restart interval (DRI); 0: the scan is one interval */
+    int32_t n_intervals;       /* ceil(MCUs / restart_interval), 1 without DRI */
+    int32_t interval_first;    /* this image's first entry in the `intervals` array (it owns n_intervals + 1 entries) */
+    int32_t reserved[3];
+    uint16_t quant[3][64];     /* per component, row-major (NOT zigzag) */
+    uint8_t dc_counts[3][16], dc_vals[3][16], ac_counts[3][16], ac_vals[3][256]; /* per component, canonical: 16 counts + values */
+} hoig_jpeg_plan;
+/* HOST, no HIP call: checks the n plans, writes each one's coef_off / plane_off and returns the workspace size in bytes (< 0: a plan
+ * is outside the supported set) */
+int64_t hoig_jpeg_decode_workspace_bytes(hoig_jpeg_plan *plans, int n);
+/* HOST twin of the entropy kernel (the same code, jpeg_entropy.h; no HIP call): bytes / plans / intervals / coef / status are host
+ * memory, coef is the workspace laid out by hoig_jpeg_decode_workspace_bytes (only the coefficient part is written: it comes first).
+ * intervals: int32 offsets relative to each image's data_off -- per image n_intervals starts, then data_len; n_entries of them in all.
+ * status[i] = 0 or HOIG_JPEG_E* bits of image i.  A bad STREAM is a status, not a return code. */
+int hoig_jpeg_entropy_host(const uint8_t *bytes, int64_t nbytes, const hoig_jpeg_plan *plans, int n, const int32_t *intervals,
+                           int64_t n_entries, void *coef, int64_t coef_bytes, int32_t *status);
+/* The batch on the device.  bytes (nbytes % 16 == 0, 16-byte aligned), plans_dev, intervals, out, status, workspace: device memory;
+ * plans_host: the same plans in host memory, read at the call (sizes and offsets are checked there; the launch geometry comes from
+ * them).  Images may differ in size.  status[i] as above, written by the device; never synchronises, allocates nothing. */
+int hoig_jpeg_decode_bgr_u8(const uint8_t *bytes, int64_t nbytes, const hoig_jpeg_plan *plans_host, const hoig_jpeg_plan *plans_dev,
+                            int n, const int32_t *intervals, int64_t n_entries, uint8_t *out, int64_t out_bytes, int32_t *status,
+                            void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
+/* The last two stages alone: the workspace already holds the coefficients (at each plan's coef_off) */
+int hoig_jpeg_reconstruct_bgr_u8(const hoig_jpeg_plan *plans_host, const hoig_jpeg_plan *plans_dev, int n, uint8_t *out,
+                                 int64_t out_bytes, void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
