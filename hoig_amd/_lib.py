@@ -219,5 +219,16 @@ def check(rc, what):
         raise HoigKernelError('%s failed: %s (code %d)' % (what, _ERR.get(rc, 'unknown'), rc))
 
 
+# Every launch of the package goes through one of these two, reached as `L.call` / `L.attempt` (an attribute of this module, read at
+# call time): a tool that rebinds the two names sees every launch (tools/op_table.py, tools/conv_table.py).
 def call(name, *args):
     check(getattr(lib, name)(*args), name)
+
+
+def attempt(name, *args):
+    """call() for an entry point that may refuse the shape: False on EUNSUPPORTED (nothing ran: the caller takes its next kernel)."""
+    rc = getattr(lib, name)(*args)
+    if rc == EUNSUPPORTED:
+        return False
+    check(rc, name)
+    return True

@@ -30,6 +30,33 @@ struct hoig_once {
 
 static inline int64_t hoig_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Launchers that one .hip file defines and another calls (the dispatchers of conv_igemm.hip walk them in turn): each takes the layers it
+// has a kernel for and returns HOIG_EUNSUPPORTED for the rest.  Declared here, where the defining file sees them too.
+// conv_small.hip: direct fp32 kernels for <= 4 / 5 output channels, the 7x7 stems with <= 8 input channels, long dot products
+int hoig_conv_small_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st);
+int hoig_conv_small_fwd_acts(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
+                             unsigned long long acts, hipStream_t st);
+int hoig_conv_small_ci_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st);
+int hoig_conv_small_dgrad(const hoig_conv_desc *d, const float *dy, const float *w, float *dx, hipStream_t st);
+int hoig_conv_small_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st);
+int hoig_conv_dot_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st);
+// conv_head16.hip: the 7x7 heads on MFMA
+int hoig_conv_head7_m16(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, unsigned long long acts,
+                        hipStream_t st);
+// conv_thin.hip: stride-1 'same' convolutions with <= 8 (3x3: 16) channels on one side, taps in place of the missing channels
+int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st,
+                       double *stats = nullptr);
+int hoig_conv_thin_dgrad(const hoig_conv_desc *d, const float *dy, const float *w, float *dx, int accumulate, hipStream_t st);
+int hoig_conv_thin_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st);
+bool hoig_conv_thin_wgrad_applies(const hoig_conv_desc *d);
+int hoig_conv_thin_out(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, unsigned long long acts,
+                       int dgrad, hipStream_t st);
+// wgrad_igemm_bf16.hip: the 16-bit weight gradients
+int hoig_conv_bf16_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, float *dbias, hipStream_t st);
+bool hoig_conv_bf16_wgrad_fuses_bias(const hoig_conv_desc *d);
+// pointwise.hip: the block registered for `st` by hoig_stream_scratch_set (nullptr: none of that size)
+namespace hoig_detail { void *stream_scratch(hipStream_t st, size_t bytes); }
+
 // Grid for HBM-bound streaming kernels: cap at 256 CUs x 8 blocks and grid-stride the rest.
 static inline int hoig_stream_grid(int64_t work_items, int block) {
     int64_t g = hoig_cdiv(work_items, block);

@@ -575,33 +575,10 @@ int check_desc(const hoig_conv_desc *d) {
 
 }  // namespace
 
-int hoig_conv_bf16_fwd_like(const hoig_conv_desc *d, const float *a, const float *w, const float *bias, float *c,
-                            bool dgrad, hipStream_t st);  // conv_igemm_bf16.hip
-int hoig_conv_small_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
-                        hipStream_t st);                  // conv_small.hip
-int hoig_conv_small_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st);
-int hoig_conv_small_dgrad(const hoig_conv_desc *d, const float *dy, const float *w, float *dx, hipStream_t st);
-int hoig_conv_small_ci_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
-                           hipStream_t st);
-int hoig_conv_dot_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st);
-int hoig_conv_small_fwd_acts(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
-                             unsigned long long acts, hipStream_t st);
-int hoig_conv_head7_m16(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, unsigned long long acts,
-                        hipStream_t st);                  // conv_head16.hip
-// conv_thin.hip: stride-1 'same' convolutions with <= 8 (3x3: 16) channels on one side, taps in place of the missing channels
-int hoig_conv_thin_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st, double *stats = nullptr);
-int hoig_conv_thin_dgrad(const hoig_conv_desc *d, const float *dy, const float *w, float *dx, int accumulate, hipStream_t st);
-int hoig_conv_thin_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st);
-int hoig_conv_thin_out(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
-                       unsigned long long acts, int dgrad, hipStream_t st);
 static unsigned long long uniform_acts(int act) {
     unsigned long long a = 0;
     for (int f = 0; f < 16; ++f) a |= (unsigned long long)(act & 15) << (4 * f);
     return a;
-}
-static bool thin_enabled() {
-    constexpr bool on = true;
-    return on;
 }
 
 extern "C" int hoig_conv2d_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
@@ -612,15 +589,11 @@ extern "C" int hoig_conv2d_fwd(const hoig_conv_desc *d, const float *x, const fl
     hipStream_t st = (hipStream_t)stream;
     rc = hoig_conv_head7_m16(d, x, w, bias, y, uniform_acts(d->act), st);      // 7x7 heads, three-term forward: MFMA, taps as columns
     if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_small_fwd(d, x, w, bias, y, st);    // ... exact fp32 / other shapes: direct fp32 kernel
-    if (rc == HOIG_EUNSUPPORTED && thin_enabled()) rc = hoig_conv_thin_out(d, x, w, bias, y, uniform_acts(d->act), 0, st);   // 3x3, <= 16 outputs
-    if (rc == HOIG_EUNSUPPORTED && thin_enabled()) rc = hoig_conv_thin_fwd(d, x, w, bias, y, st);      // thin-input convs on MFMA
+    if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_thin_out(d, x, w, bias, y, uniform_acts(d->act), 0, st);   // 3x3, <= 16 outputs
+    if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_thin_fwd(d, x, w, bias, y, st);      // thin-input convs on MFMA
     if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_small_ci_fwd(d, x, w, bias, y, st);    // 7x7 stems with <= 8 input channels
     if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_dot_fwd(d, x, w, bias, y, st);         // <= 4 outputs over >= 1024 products
     if (rc != HOIG_EUNSUPPORTED) return rc;
-    if (d->precision != HOIG_PREC_F32) {
-        rc = hoig_conv_bf16_fwd_like(d, x, w, bias, y, false, st);
-        if (rc != HOIG_EUNSUPPORTED) return rc;
-    }
     IgemmArgs a;
     a.A = x; a.W = w; a.bias = bias; a.C = y;
     a.g = make_geom(d, true, d->transposed != 0);
@@ -637,7 +610,6 @@ extern "C" int hoig_conv2d_fwd_stats(const hoig_conv_desc *d, const float *x, co
     int rc = check_desc(d);
     if (rc) return rc;
     if (!x || !w || !y || !stats) return HOIG_EINVAL;
-    if (!thin_enabled()) return HOIG_EUNSUPPORTED;
     return hoig_conv_thin_fwd(d, x, w, bias, y, (hipStream_t)stream, stats);
 }
 
@@ -660,14 +632,10 @@ extern "C" int hoig_conv2d_bwd_data(const hoig_conv_desc *d, const float *dy, co
     if (rc) return rc;
     if (!dy || !w || !dx) return HOIG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    rc = thin_enabled() ? hoig_conv_thin_dgrad(d, dy, w, dx, 0, st) : HOIG_EUNSUPPORTED;     // thin-output convs (heads) on MFMA
-    if (rc == HOIG_EUNSUPPORTED && thin_enabled()) rc = hoig_conv_thin_out(d, dy, w, nullptr, dx, 0, 1, st);   // thin-INPUT convs (VGG conv1_1)
+    rc = hoig_conv_thin_dgrad(d, dy, w, dx, 0, st);     // thin-output convs (heads) on MFMA
+    if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_thin_out(d, dy, w, nullptr, dx, 0, 1, st);   // thin-INPUT convs (VGG conv1_1)
     if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_small_dgrad(d, dy, w, dx, st);     // ... or the direct fp32 kernel (HOIG_PREC_F32)
     if (rc != HOIG_EUNSUPPORTED) return rc;
-    if (d->precision != HOIG_PREC_F32) {
-        rc = hoig_conv_bf16_fwd_like(d, dy, w, nullptr, dx, true, st);
-        if (rc != HOIG_EUNSUPPORTED) return rc;
-    }
     IgemmArgs a;
     a.A = dy; a.W = w; a.bias = nullptr; a.C = dx;
     a.g = make_geom(d, false, d->transposed == 0);
@@ -700,14 +668,10 @@ static int launch_wgrad(WgradArgs a, hipStream_t st) {
     return HOIG_OK;
 }
 
-int hoig_conv_bf16_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, float *dbias, hipStream_t st);
-bool hoig_conv_bf16_wgrad_fuses_bias(const hoig_conv_desc *d);
-
-bool hoig_conv_thin_wgrad_applies(const hoig_conv_desc *d);       // conv_thin.hip
 // bytes of per-stream scratch (hoig_stream_scratch_set) hoig_conv2d_bwd_weight wants for this layer: 0 for all but the thin-channel ones
 extern "C" int64_t hoig_conv2d_bwd_weight_scratch_bytes(const hoig_conv_desc *d) {
     if (!d || check_desc(d)) return 0;
-    return (thin_enabled() && hoig_conv_thin_wgrad_applies(d)) ? hoig_stream_scratch_bytes() : 0;
+    return hoig_conv_thin_wgrad_applies(d) ? hoig_stream_scratch_bytes() : 0;
 }
 
 extern "C" int hoig_conv2d_bwd_weight(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, float *dbias,
@@ -721,7 +685,7 @@ extern "C" int hoig_conv2d_bwd_weight(const hoig_conv_desc *d, const float *x, c
         rc = hoig_colsum_accum(dy, dbias, (int64_t)d->B * d->Ho * d->Wo, d->Co, stream);
         if (rc) return rc;
     }
-    rc = thin_enabled() ? hoig_conv_thin_wgrad(d, x, dy, dw, st) : HOIG_EUNSUPPORTED;      // thin-input / thin-output convs on MFMA
+    rc = hoig_conv_thin_wgrad(d, x, dy, dw, st);     // thin-input / thin-output convs on MFMA
     if (rc == HOIG_EUNSUPPORTED) rc = hoig_conv_small_wgrad(d, x, dy, dw, st);
     if (rc != HOIG_EUNSUPPORTED) return rc;
     if (d->precision != HOIG_PREC_F32) {

@@ -1419,10 +1419,37 @@ struct PairSet {
     float *c;
 };
 
-int run(const hoig_conv_desc *d, const float *a, const unsigned short *wh, const unsigned short *wl, const float *bias,
-        float *c, bool dgrad, hipStream_t st, const float *a2 = nullptr, int cg1 = 0, float *c2 = nullptr, int n1 = 0,
-        const float *addend = nullptr, double *stats = nullptr, bool a_split = false, const PairSet *g2 = nullptr,
-        const InNorm *in = nullptr) {
+// One launch of the packed-plane dispatcher; an entry point fills the fields it uses.
+struct Conv {
+    const hoig_conv_desc *d = nullptr;
+    const float *a = nullptr;                        // the gathered tensor: x (forward) / dy (data gradient)
+    const unsigned short *wh = nullptr, *wl = nullptr;
+    const float *bias = nullptr;
+    float *c = nullptr;                              // the output: y / dx
+    bool dgrad = false;
+    hipStream_t st = nullptr;
+    const float *a2 = nullptr;                       // second input: the gathered tensor is [a | a2], a holds cg1 channels
+    int cg1 = 0;
+    float *c2 = nullptr;                             // second output: [c | c2], c holds n1 channels
+    int n1 = 0;
+    const float *addend = nullptr;                   // added to the output in the epilogue
+    double *stats = nullptr;                         // per-image channel sums of the output (hoig_stats_add)
+    bool a_split = false;                            // a holds pre-split bf16 hi | lo planes
+    const PairSet *g2 = nullptr;
+    const InNorm *in = nullptr;
+};
+
+int run(const Conv &q) {
+    const hoig_conv_desc *d = q.d;
+    const float *a = q.a, *bias = q.bias, *a2 = q.a2, *addend = q.addend;
+    const unsigned short *wh = q.wh, *wl = q.wl;
+    float *c = q.c, *c2 = q.c2;
+    const bool dgrad = q.dgrad, a_split = q.a_split;
+    const int cg1 = q.cg1, n1 = q.n1;
+    double *stats = q.stats;
+    const PairSet *g2 = q.g2;
+    const InNorm *in = q.in;
+    hipStream_t st = q.st;
     if (in && (dgrad || d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->transposed || a_split || g2))
         return HOIG_EUNSUPPORTED;
     Args p;
@@ -1558,12 +1585,6 @@ int run(const hoig_conv_desc *d, const float *a, const unsigned short *wh, const
 
 }  // namespace
 
-// fp32-weight entry points cannot use the bf16 path (it needs the pre-split planes): tell the dispatcher to fall back.
-int hoig_conv_bf16_fwd_like(const hoig_conv_desc *, const float *, const float *, const float *, float *, bool,
-                            hipStream_t) {
-    return HOIG_EUNSUPPORTED;
-}
-
 extern "C" int hoig_pack_conv_weight_bf16(const float *w, int Co, int RS, int Ci, int for_dgrad, uint16_t *hi,
                                           uint16_t *lo, hoig_stream_t stream) {
     if (!w || !hi || Co <= 0 || RS <= 0 || Ci <= 0) return HOIG_EINVAL;
@@ -1600,14 +1621,14 @@ extern "C" int hoig_conv2d_fwd_packed(const hoig_conv_desc *d, const float *x, c
                                       const float *bias, float *y, hoig_stream_t stream) {
     if (!d || !x || !w_hi || !y) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, x, w_hi, w_lo, bias, y, false, (hipStream_t)stream);
+    return run(Conv{.d = d, .a = x, .wh = w_hi, .wl = w_lo, .bias = bias, .c = y, .st = (hipStream_t)stream});
 }
 
 extern "C" int hoig_conv2d_bwd_data_packed(const hoig_conv_desc *d, const float *dy, const uint16_t *wt_hi,
                                            const uint16_t *wt_lo, float *dx, hoig_stream_t stream) {
     if (!d || !dy || !wt_hi || !dx) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, dy, wt_hi, wt_lo, nullptr, dx, true, (hipStream_t)stream);
+    return run(Conv{.d = d, .a = dy, .wh = wt_hi, .wl = wt_lo, .c = dx, .dgrad = true, .st = (hipStream_t)stream});
 }
 
 // y = conv(x) and, from the same epilogue, stats[b][0/1][co] += sum / sum of squares of y over image b (HOIG_EUNSUPPORTED where the
@@ -1616,14 +1637,14 @@ extern "C" int hoig_conv2d_fwd_packed_stats(const hoig_conv_desc *d, const float
                                             const float *bias, float *y, double *stats, hoig_stream_t stream) {
     if (!d || !x || !w_hi || !y || !stats) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, x, w_hi, w_lo, bias, y, false, (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, stats);
+    return run(Conv{.d = d, .a = x, .wh = w_hi, .wl = w_lo, .bias = bias, .c = y, .st = (hipStream_t)stream, .stats = stats});
 }
 extern "C" int hoig_conv2d_cat_fwd_packed_stats(const hoig_conv_desc *d, const float *x1, int C1, const float *x2,
                                                 const uint16_t *w_hi, const uint16_t *w_lo, const float *bias, float *y,
                                                 double *stats, hoig_stream_t stream) {
     if (!d || !x1 || !x2 || !w_hi || !y || !stats) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, x1, w_hi, w_lo, bias, y, false, (hipStream_t)stream, x2, C1, nullptr, 0, nullptr, stats);
+    return run(Conv{.d = d, .a = x1, .wh = w_hi, .wl = w_lo, .bias = bias, .c = y, .st = (hipStream_t)stream, .a2 = x2, .cg1 = C1, .stats = stats});
 }
 
 // forward of conv -> instance norm (+ affine) -> ReLU -> THIS 3x3 stride-1 convolution in INFERENCE: x (and x2) are RAW, the loader
@@ -1634,7 +1655,8 @@ extern "C" int hoig_conv2d_fwd_packed_normin(const hoig_conv_desc *d, const floa
     if (!d || !x || !w_hi || !y || !in_scale || !in_shift || in_relu_c0 < 0) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     const InNorm in{in_scale, in_shift, in_relu_c0};
-    return run(d, x, w_hi, w_lo, bias, y, false, (hipStream_t)stream, x2, x2 ? C1 : 0, nullptr, 0, nullptr, stats, false, nullptr, &in);
+    return run(Conv{.d = d, .a = x, .wh = w_hi, .wl = w_lo, .bias = bias, .c = y, .st = (hipStream_t)stream, .a2 = x2, .cg1 = x2 ? C1 : 0,
+                    .stats = stats, .in = &in});
 }
 
 // dx = data gradient + addend (HOIG_EUNSUPPORTED where the layer's kernel has no such epilogue: the caller adds separately)
@@ -1642,7 +1664,7 @@ extern "C" int hoig_conv2d_bwd_data_packed_add(const hoig_conv_desc *d, const fl
                                                const uint16_t *wt_lo, const float *addend, float *dx, hoig_stream_t stream) {
     if (!d || !dy || !wt_hi || !dx || !addend) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, dy, wt_hi, wt_lo, nullptr, dx, true, (hipStream_t)stream, nullptr, 0, nullptr, 0, addend);
+    return run(Conv{.d = d, .a = dy, .wh = wt_hi, .wl = wt_lo, .c = dx, .dgrad = true, .st = (hipStream_t)stream, .addend = addend});
 }
 
 // data gradient (+ addend, nullable) from PRE-SPLIT dy (include/hoig_kernels.h): the 3x3 stride-1 "same" layers on conv_halo16.hip
@@ -1651,8 +1673,8 @@ extern "C" int hoig_conv2d_bwd_data_packed_split(const hoig_conv_desc *d, const 
     if (!d || !dy_split || !wt_hi || !dx) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     if (d->precision == HOIG_PREC_BF16X3 || d->transposed || d->stride != 1 || d->R != 3 || d->S != 3) return HOIG_EUNSUPPORTED;
-    return run(d, reinterpret_cast<const float *>(dy_split), wt_hi, wt_lo, nullptr, dx, true, (hipStream_t)stream, nullptr, 0, nullptr, 0,
-               addend, nullptr, true);
+    return run(Conv{.d = d, .a = reinterpret_cast<const float *>(dy_split), .wh = wt_hi, .wl = wt_lo, .c = dx, .dgrad = true,
+                    .st = (hipStream_t)stream, .addend = addend, .a_split = true});
 }
 
 // GROUPED launches (include/hoig_kernels.h): two convolutions of ONE descriptor -- different tensors, different weights -- as one grid
@@ -1663,7 +1685,7 @@ extern "C" int hoig_conv2d_fwd_packed_pair(const hoig_conv_desc *d, const float 
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
     if (d->transposed || d->stride != 1 || d->R != 3 || d->S != 3) return HOIG_EUNSUPPORTED;
     const PairSet g2{xb, wb_hi, wb_lo, bias_b, nullptr, yb};
-    return run(d, xa, wa_hi, wa_lo, bias_a, ya, false, (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, nullptr, false, &g2);
+    return run(Conv{.d = d, .a = xa, .wh = wa_hi, .wl = wa_lo, .bias = bias_a, .c = ya, .st = (hipStream_t)stream, .g2 = &g2});
 }
 extern "C" int hoig_conv2d_bwd_data_packed_split_pair(const hoig_conv_desc *d, const uint16_t *dys_a, const uint16_t *dys_b,
                                                       const uint16_t *wta_hi, const uint16_t *wta_lo, const uint16_t *wtb_hi,
@@ -1674,8 +1696,8 @@ extern "C" int hoig_conv2d_bwd_data_packed_split_pair(const hoig_conv_desc *d, c
     if (d->precision == HOIG_PREC_BF16X3 || d->transposed || d->stride != 1 || d->R != 3 || d->S != 3) return HOIG_EUNSUPPORTED;
     if ((addend_a == nullptr) != (addend_b == nullptr)) return HOIG_EINVAL;
     const PairSet g2{reinterpret_cast<const float *>(dys_b), wtb_hi, wtb_lo, nullptr, addend_b, dxb};
-    return run(d, reinterpret_cast<const float *>(dys_a), wta_hi, wta_lo, nullptr, dxa, true, (hipStream_t)stream, nullptr, 0, nullptr, 0,
-               addend_a, nullptr, true, &g2);
+    return run(Conv{.d = d, .a = reinterpret_cast<const float *>(dys_a), .wh = wta_hi, .wl = wta_lo, .c = dxa, .dgrad = true,
+                    .st = (hipStream_t)stream, .addend = addend_a, .a_split = true, .g2 = &g2});
 }
 
 // conv(cat[x1, x2]) and its data gradient [dx1 | dx2] without materialising the concatenation (3x3 stride-1 "same" only)
@@ -1684,13 +1706,13 @@ extern "C" int hoig_conv2d_cat_fwd_packed(const hoig_conv_desc *d, const float *
                                           hoig_stream_t stream) {
     if (!d || !x1 || !x2 || !w_hi || !y) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, x1, w_hi, w_lo, bias, y, false, (hipStream_t)stream, x2, C1, nullptr, 0);
+    return run(Conv{.d = d, .a = x1, .wh = w_hi, .wl = w_lo, .bias = bias, .c = y, .st = (hipStream_t)stream, .a2 = x2, .cg1 = C1});
 }
 extern "C" int hoig_conv2d_cat_bwd_data_packed(const hoig_conv_desc *d, const float *dy, const uint16_t *wt_hi,
                                                const uint16_t *wt_lo, float *dx1, int C1, float *dx2,
                                                hoig_stream_t stream) {
     if (!d || !dy || !wt_hi || !dx1 || !dx2) return HOIG_EINVAL;
     if (!is_16bit_precision(d->precision)) return HOIG_EINVAL;
-    return run(d, dy, wt_hi, wt_lo, nullptr, dx1, true, (hipStream_t)stream, nullptr, 0, dx2, C1);
+    return run(Conv{.d = d, .a = dy, .wh = wt_hi, .wl = wt_lo, .c = dx1, .dgrad = true, .st = (hipStream_t)stream, .c2 = dx2, .n1 = C1});
 }
 

@@ -481,9 +481,6 @@ __global__ __launch_bounds__(NTHR) void thin_reduce_kernel(const ThinArgs p, int
 
 // Workspace for the partials: the launching stream's scratch block, which the CALLER owns and registers
 // (hoig_stream_scratch_set, pointwise.hip); without one the kernel falls back to atomics.
-}  // namespace
-namespace hoig_detail { void *stream_scratch(hipStream_t st, size_t bytes); }
-namespace {
 constexpr size_t WS_SLOT_BYTES = (size_t)16 << 20;      // = hoig_stream_scratch_bytes(): what a caller registers per stream
 float *thin_workspace(hipStream_t st, size_t bytes) { return static_cast<float *>(hoig_detail::stream_scratch(st, bytes)); }
 

@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops as O
-from .._lib import call, ConvDesc
+from .._lib import ConvDesc
 
 # Three-term 16-bit forward (HOIG_PREC_BF16X3: products to ~2^-21, fp32 accumulation) meets the metric tolerances of
 # tests/test_metrics_gpu.py; 'f32' (exact fp32 products) is the parity mode.
@@ -76,21 +76,21 @@ def pool2d(x, k, stride, pad_h=0, pad_w=0, mode=L.POOL_MAX, count_include_pad=Tr
     B, H, W, C = x.shape
     Ho, Wo = (H + 2 * pad_h - k) // stride + 1, (W + 2 * pad_w - k) // stride + 1
     y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
-    call('hoig_pool2d_fwd', O._p(x), O._p(y), B, H, W, C, k, stride, pad_h, pad_w, mode, 1 if count_include_pad else 0, O._st())
+    L.call('hoig_pool2d_fwd', O._p(x), O._p(y), B, H, W, C, k, stride, pad_h, pad_w, mode, 1 if count_include_pad else 0, O._st())
     return y
 
 
 def pad2d(x, pad_h, pad_w):
     B, H, W, C = x.shape
     y = torch.empty((B, H + 2 * pad_h, W + 2 * pad_w, C), dtype=torch.float32, device=x.device)
-    call('hoig_pad2d', O._p(x), O._p(y), B, H, W, C, pad_h, pad_w, O._st())
+    L.call('hoig_pad2d', O._p(x), O._p(y), B, H, W, C, pad_h, pad_w, O._st())
     return y
 
 
 def global_avgpool(x):
     B, H, W, C = x.shape
     y = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    call('hoig_global_avgpool', O._p(x), O._p(y), B, H * W, C, O._st())
+    L.call('hoig_global_avgpool', O._p(x), O._p(y), B, H * W, C, O._st())
     return y
 
 
@@ -101,7 +101,7 @@ def cat_channels(parts):
     npix = y.numel() // C
     off = 0
     for p in parts:
-        call('hoig_copy_channels', O._p(p), O._p(y), npix, p.shape[-1], 0, C, off, p.shape[-1], 0, O._st())
+        L.call('hoig_copy_channels', O._p(p), O._p(y), npix, p.shape[-1], 0, C, off, p.shape[-1], 0, O._st())
         off += p.shape[-1]
     return y
 
@@ -115,7 +115,7 @@ def stage_images_u8(u8, size=None, steps=()):
     flat = [v for sub, div in steps for v in (list(sub) + list(div))]
     aff = (ctypes.c_float * max(len(flat), 1))(*flat)
     y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=u8.device)
-    call('hoig_stage_images_u8', O._p(u8), O._p(y), B, H, W, C, Ho, Wo, len(steps), ctypes.cast(aff, ctypes.c_void_p), O._st())
+    L.call('hoig_stage_images_u8', O._p(u8), O._p(y), B, H, W, C, Ho, Wo, len(steps), ctypes.cast(aff, ctypes.c_void_p), O._st())
     return y
 
 

@@ -10,7 +10,6 @@ import torch
 
 from .. import _lib as L
 from .. import ops as O
-from .._lib import call
 from . import images as I
 from . import kernels as K
 from .weights import ALEXNET_FILE, LPIPS_FILE, hub_path, resolve, take
@@ -68,7 +67,7 @@ class LPIPS(object):
             work = torch.zeros(ws, dtype=torch.uint8, device=xy.device)
             for f, w in zip(fmaps, self.heads):
                 _, H, W, C = f.shape
-                call('hoig_lpips_layer', O._p(f), O._p(f[n:]), O._p(w), O._p(out), n, H * W, C, O._p(work), O._st())
+                L.call('hoig_lpips_layer', O._p(f), O._p(f[n:]), O._p(w), O._p(out), n, H * W, C, O._p(work), O._st())
         return out
 
     def forward(self, x, y):

@@ -8,7 +8,6 @@ import torch
 
 from .. import _lib as L
 from .. import ops as O
-from .._lib import call
 from . import images as I
 from . import kernels as KR
 
@@ -25,8 +24,8 @@ def _level(xy, data_range, win_size, win_sigma, K_):
     if nbytes < 0:
         raise ValueError('image %dx%d is smaller than the %d-tap window' % (H, W, win_size))
     work = torch.zeros(nbytes, dtype=torch.uint8, device=xy.device)
-    call('hoig_ssim', O._p(xy), O._p(xy[n:]), O._p(s), O._p(cs), n, H, W, C, float(data_range), float(K_[0]), float(K_[1]), win_size,
-         float(win_sigma), O._p(work), O._st())
+    L.call('hoig_ssim', O._p(xy), O._p(xy[n:]), O._p(s), O._p(cs), n, H, W, C, float(data_range), float(K_[0]), float(K_[1]), win_size,
+           float(win_sigma), O._p(work), O._st())
     return s, cs
 
 

@@ -1,13 +1,11 @@
 """The local-attention operators and the reference's two CUDA-extension drop-ins (split off hoig_amd/ops.py in round 6; re-exported there)."""
-import contextlib
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from ._lib import call, ConvDesc
-from . import ops as _o          # (names of the core module are read at call time: _bwd_descs, _chk, _conv_dgrad_raw, _conv_fwd_raw, _grad_epoch, _grad_target, _p, _st, _wgrad_hold, _wgrad_side_stream, packed_strides, precision, wgrad_call)
+from ._lib import ConvDesc
+from . import ops as _o          # (for the names that are rebound at run time, see ops._reexport: _conv_dgrad_raw, _conv_fwd_raw, precision)
+from .ops import _bwd_descs, _chk, _grad_epoch, _grad_target, _p, _st, _wgrad_launch, packed_strides
 
 _attn_index = {}
 
@@ -24,7 +22,7 @@ def _attn_pixel_index(flow, B, H, W):
     hit = _attn_index.get(key)
     if hit is None:
         idx = torch.empty(L.lib.hoig_attn_index_ints(B, H, W), dtype=torch.int32, device=flow.device)
-        call('hoig_attn_build_index', _o._p(flow), _o._p(idx), B, H, W, _o._st())
+        L.call('hoig_attn_build_index', _p(flow), _p(idx), B, H, W, _st())
         hit = _attn_index[key] = (idx, flow)           # (the flow is held so that its address is not reused meanwhile)
     return hit[0]
 
@@ -36,17 +34,17 @@ class _AttnSourceConv(Function):
 
     @staticmethod
     def forward(ctx, source, ws, prec, fork=False):
-        _o._chk(source)
-        _o._chk(ws)
+        _chk(source)
+        _chk(ws)
         B, H, W, C = source.shape
-        assert tuple(ws.shape) == (128, C, 5, 5) and tuple(ws.stride()) == _o.packed_strides(ws.shape, False)
+        assert tuple(ws.shape) == (128, C, 5, 5) and tuple(ws.stride()) == packed_strides(ws.shape, False)
         spad = torch.empty((B, H + 8, W + 8, C), dtype=source.dtype, device=source.device)
-        call('hoig_replicate_pad_fwd', _o._p(source), _o._p(spad), B, H, W, C, 4, _o._st())
+        L.call('hoig_replicate_pad_fwd', _p(source), _p(spad), B, H, W, C, 4, _st())
         d_s = ConvDesc(B, H + 8, W + 8, C, H + 4, W + 4, 128, 5, 5, 1, 0, 0, L.ACT_NONE, 0.0, prec)
         gs = torch.empty((B, H + 4, W + 4, 128), dtype=source.dtype, device=source.device)
         _o._conv_fwd_raw(d_s, spad, ws, None, gs)
         ctx.save_for_backward(ws, spad)
-        ctx.descs = _o._bwd_descs(d_s)
+        ctx.descs = _bwd_descs(d_s)
         ctx.shape = (B, H, W, C)
         if fork:                              # (gs, source): see _Conv.forward
             ctx.set_materialize_grads(False)
@@ -55,29 +53,22 @@ class _AttnSourceConv(Function):
 
     @staticmethod
     def backward(ctx, dgs, dsrc_r=None):
-        _o._grad_epoch()
+        _grad_epoch()
         ws, spad = ctx.saved_tensors
         ds_dg, ds_wg = ctx.descs
         B, H, W, C = ctx.shape
         if dgs is None:
             return dsrc_r, None, None, None
         dgs = dgs.contiguous()
-        gw, ret_w = _o._grad_target(ws)
-        side = _o._wgrad_side_stream(dgs.device) if not ret_w else None
-        if side is not None:          # (see _Conv.backward)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                _o.wgrad_call('hoig_conv2d_bwd_weight', ds_wg, _o._p(spad), _o._p(dgs), _o._p(gw), None, _o._st())
-            _o._wgrad_hold(side, (spad, dgs))
-        else:
-            _o.wgrad_call('hoig_conv2d_bwd_weight', ds_wg, _o._p(spad), _o._p(dgs), _o._p(gw), None, _o._st())
+        gw, ret_w = _grad_target(ws)
+        _wgrad_launch(dgs.device, ret_w, (spad, dgs), 'hoig_conv2d_bwd_weight', ds_wg, _p(spad), _p(dgs), _p(gw), None)
         dsrc = None
         if ctx.needs_input_grad[0]:
             dspad = torch.empty_like(spad)
             _o._conv_dgrad_raw(ds_dg, dgs, ws, dspad)
             dsrc = torch.empty((B, H, W, C), dtype=dgs.dtype, device=dgs.device)
-            call('hoig_replicate_pad_bwd_add', _o._p(dspad), _o._p(dsrc_r.contiguous() if dsrc_r is not None else None), _o._p(dsrc),
-                 B, H, W, C, 4, _o._st())                                                           # (writes every element)
+            L.call('hoig_replicate_pad_bwd_add', _p(dspad), _p(dsrc_r.contiguous() if dsrc_r is not None else None), _p(dsrc),
+                   B, H, W, C, 4, _st())                                                           # (writes every element)
         return dsrc, (gw if ret_w else None), None, None
 
 
@@ -91,9 +82,9 @@ class _LocalAttn(Function):
     @staticmethod
     def forward(ctx, source, target, flow, gs, wt, b1, w2, b2, prec, fork=False):
         for t in (source, target, flow, gs, wt, b1, w2, b2):
-            _o._chk(t)
+            _chk(t)
         B, H, W, C = source.shape
-        assert tuple(wt.shape) == (128, C, 5, 5) and tuple(wt.stride()) == _o.packed_strides(wt.shape, False)
+        assert tuple(wt.shape) == (128, C, 5, 5) and tuple(wt.stride()) == packed_strides(wt.shape, False)
         assert tuple(gs.shape) == (B, H + 4, W + 4, 128)
         M = B * H * W
         # the backward's gather kernels (hoig_attn_src_gather / hoig_attn_build_index) cover less than the forward does: say so
@@ -103,7 +94,7 @@ class _LocalAttn(Function):
                                       'W < 2040 (got C=%d, B*H*W=%d, W=%d)' % (C, M, W))
         dev, dt = source.device, source.dtype
         tpad = torch.empty((B, H + 4, W + 4, C), dtype=dt, device=dev)
-        call('hoig_replicate_pad_fwd', _o._p(target), _o._p(tpad), B, H, W, C, 2, _o._st())
+        L.call('hoig_replicate_pad_fwd', _p(target), _p(tpad), B, H, W, C, 2, _st())
         d_t = ConvDesc(B, H + 4, W + 4, C, H, W, 128, 5, 5, 1, 0, 0, L.ACT_NONE, 0.0, prec)
         gt = torch.empty((M, 128), dtype=dt, device=dev)
         _o._conv_fwd_raw(d_t, tpad, wt, b1, gt)
@@ -111,10 +102,10 @@ class _LocalAttn(Function):
         attn = torch.empty((M, 25), dtype=dt, device=dev)
         out = torch.empty_like(source)
         kf = torch.empty((M, 36), dtype=dt, device=dev) if source.requires_grad else None
-        call('hoig_attn_pixel_fwd', _o._p(gt), _o._p(gs), _o._p(flow), _o._p(w2), _o._p(b2), _o._p(source), _o._p(hidden), _o._p(attn), _o._p(out),
-             _o._p(kf), B, H, W, C, _o._st())
+        L.call('hoig_attn_pixel_fwd', _p(gt), _p(gs), _p(flow), _p(w2), _p(b2), _p(source), _p(hidden), _p(attn), _p(out),
+               _p(kf), B, H, W, C, _st())
         ctx.save_for_backward(source, flow, wt, b1, w2, b2, tpad, hidden, attn, kf)
-        ctx.descs = _o._bwd_descs(d_t)
+        ctx.descs = _bwd_descs(d_t)
         ctx.shape = (B, H, W, C)
         if fork:
             # (out, source, target): both feature maps have further readers (the next layer of their chain; the sum
@@ -126,42 +117,36 @@ class _LocalAttn(Function):
 
     @staticmethod
     def backward(ctx, dout, dsrc_r=None, dtgt_r=None):
-        _o._grad_epoch()
+        _grad_epoch()
         source, flow, wt, b1, w2, b2, tpad, hidden, attn, kf = ctx.saved_tensors
         dt_dg, dt_wg = ctx.descs
         B, H, W, C = ctx.shape
         if dout is None:
             return (dsrc_r, dtgt_r) + (None,) * 8
         dout = dout.contiguous()
-        gs = [_o._grad_target(p) for p in (wt, b1, w2, b2)]
+        gs = [_grad_target(p) for p in (wt, b1, w2, b2)]
         dhid = torch.empty_like(hidden)                       # = dGt
         e_ws = torch.empty((B * H * W, 36), dtype=dout.dtype, device=dout.device)
-        call('hoig_attn_pixel_bwd', _o._p(hidden), _o._p(attn), _o._p(w2), _o._p(source), _o._p(flow), _o._p(dout), _o._p(dhid), _o._p(gs[2][0]),
-             _o._p(gs[3][0]), _o._p(e_ws), B, H, W, C, _o._st())
+        L.call('hoig_attn_pixel_bwd', _p(hidden), _p(attn), _p(w2), _p(source), _p(flow), _p(dout), _p(dhid), _p(gs[2][0]),
+               _p(gs[3][0]), _p(e_ws), B, H, W, C, _st())
         index = _attn_pixel_index(flow, B, H, W)
         dgs = None
         if ctx.needs_input_grad[3]:
             dgs = torch.empty((B, H + 4, W + 4, 128), dtype=dout.dtype, device=dout.device)
-            call('hoig_attn_gs_gather', _o._p(index), _o._p(flow), _o._p(dhid), _o._p(dgs), B, H, W, _o._st())
-        side = _o._wgrad_side_stream(dout.device) if not any(r for _, r in gs) else None
-        if side is not None:          # (see _Conv.backward)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                _o.wgrad_call('hoig_conv2d_bwd_weight', dt_wg, _o._p(tpad), _o._p(dhid), _o._p(gs[0][0]), _o._p(gs[1][0]), _o._st())
-            _o._wgrad_hold(side, (tpad, dhid))
-        else:
-            _o.wgrad_call('hoig_conv2d_bwd_weight', dt_wg, _o._p(tpad), _o._p(dhid), _o._p(gs[0][0]), _o._p(gs[1][0]), _o._st())
+            L.call('hoig_attn_gs_gather', _p(index), _p(flow), _p(dhid), _p(dgs), B, H, W, _st())
+        _wgrad_launch(dout.device, any(r for _, r in gs), (tpad, dhid),
+                      'hoig_conv2d_bwd_weight', dt_wg, _p(tpad), _p(dhid), _p(gs[0][0]), _p(gs[1][0]))
         dtgt = dsrc = None
         if ctx.needs_input_grad[1]:
             dtpad = torch.empty_like(tpad)
             _o._conv_dgrad_raw(dt_dg, dhid, wt, dtpad)
             dtgt = torch.empty((B, H, W, C), dtype=dout.dtype, device=dout.device)
-            call('hoig_replicate_pad_bwd_add', _o._p(dtpad), _o._p(dtgt_r.contiguous() if dtgt_r is not None else None), _o._p(dtgt),
-                 B, H, W, C, 2, _o._st())
+            L.call('hoig_replicate_pad_bwd_add', _p(dtpad), _p(dtgt_r.contiguous() if dtgt_r is not None else None), _p(dtgt),
+                   B, H, W, C, 2, _st())
         if ctx.needs_input_grad[0]:                           # the weighted average's part (Gs's part comes from _AttnSourceConv)
             dsrc = torch.empty((B, H, W, C), dtype=dout.dtype, device=dout.device)
-            call('hoig_attn_src_gather', _o._p(index), _o._p(kf), _o._p(dout), _o._p(dsrc_r.contiguous() if dsrc_r is not None else None),
-                 _o._p(dsrc), B, H, W, C, _o._st())
+            L.call('hoig_attn_src_gather', _p(index), _p(kf), _p(dout), _p(dsrc_r.contiguous() if dsrc_r is not None else None),
+                   _p(dsrc), B, H, W, C, _st())
         rets = [g if r else None for g, r in gs]
         return dsrc, dtgt, None, dgs, rets[0], rets[1], rets[2], rets[3], None, None
 
@@ -194,12 +179,12 @@ def local_attention(source, target, flow, wt, ws, b1, w2, b2, prec=None, gs=None
 class _BlockExtractor(Function):
     @staticmethod
     def forward(ctx, source, flow, k):
-        _o._chk(source); _o._chk(flow)
+        _chk(source); _chk(flow)
         assert source.is_contiguous() and flow.is_contiguous() and flow.shape[1] == 2
         B, C, Hs, Ws = source.shape
         Hf, Wf = flow.shape[2], flow.shape[3]
         out = source.new_zeros((B, C, k * Hf, k * Wf))
-        call('hoig_block_extractor_forward', _o._p(source), _o._p(flow), _o._p(out), B, C, Hs, Ws, Hf, Wf, k, _o._st())
+        L.call('hoig_block_extractor_forward', _p(source), _p(flow), _p(out), B, C, Hs, Ws, Hf, Wf, k, _st())
         ctx.save_for_backward(source, flow)
         ctx.k = k
         return out
@@ -210,8 +195,8 @@ class _BlockExtractor(Function):
         B, C, Hs, Ws = source.shape
         Hf, Wf = flow.shape[2], flow.shape[3]
         gs, gf = torch.zeros_like(source), torch.zeros_like(flow)
-        call('hoig_block_extractor_backward', _o._p(source), _o._p(flow), _o._p(g.contiguous()), _o._p(gs), _o._p(gf), B, C, Hs, Ws,
-             Hf, Wf, ctx.k, _o._st())
+        L.call('hoig_block_extractor_backward', _p(source), _p(flow), _p(g.contiguous()), _p(gs), _p(gf), B, C, Hs, Ws,
+               Hf, Wf, ctx.k, _st())
         return gs, gf, None
 
 
@@ -222,11 +207,11 @@ def block_extractor(source, flow, kernel_size):
 class _LocalAttnReshape(Function):
     @staticmethod
     def forward(ctx, x, k):
-        _o._chk(x)
+        _chk(x)
         B, C, Hs, Ws = x.shape
         assert C == k * k
         out = x.new_zeros((B, 1, k * Hs, k * Ws))
-        call('hoig_local_attn_reshape_forward', _o._p(x), _o._p(out), B, Hs, Ws, k, _o._st())
+        L.call('hoig_local_attn_reshape_forward', _p(x), _p(out), B, Hs, Ws, k, _st())
         ctx.cfg = (B, Hs, Ws, k)
         return out
 
@@ -234,7 +219,7 @@ class _LocalAttnReshape(Function):
     def backward(ctx, g):
         B, Hs, Ws, k = ctx.cfg
         gi = g.new_zeros((B, k * k, Hs, Ws))
-        call('hoig_local_attn_reshape_backward', _o._p(g.contiguous()), _o._p(gi), B, Hs, Ws, k, _o._st())
+        L.call('hoig_local_attn_reshape_backward', _p(g.contiguous()), _p(gi), B, Hs, Ws, k, _st())
         return gi, None
 
 

@@ -1,24 +1,20 @@
 """Image composition, the loss terms and the eval output conversion (split off hoig_amd/ops.py in round 6; re-exported there)."""
-import contextlib
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from ._lib import call, ConvDesc
-from . import ops as _o          # (names of the core module are read at call time: _chk, _p, _st)
+from .ops import _chk, _p, _st
 
 # ------------------------------------------------------------------------------------------------- compose / losses
 class _Compose(Function):
     @staticmethod
     def forward(ctx, bg, obj, hand, mbg, mh):
         for t in (bg, obj, hand, mbg, mh):
-            _o._chk(t)
+            _chk(t)
         C = bg.shape[-1]
         npix = bg.numel() // C
         img = torch.empty_like(bg)
-        call('hoig_compose_fwd', _o._p(bg), _o._p(obj), _o._p(hand), _o._p(mbg), _o._p(mh), _o._p(img), npix, C, _o._st())
+        L.call('hoig_compose_fwd', _p(bg), _p(obj), _p(hand), _p(mbg), _p(mh), _p(img), npix, C, _st())
         ctx.save_for_backward(bg, obj, hand, mbg, mh)
         return img
 
@@ -29,8 +25,8 @@ class _Compose(Function):
         npix = bg.numel() // C
         dbg, dobj, dhand = torch.empty_like(bg), torch.empty_like(obj), torch.empty_like(hand)
         dmbg, dmh = torch.empty_like(mbg), torch.empty_like(mh)
-        call('hoig_compose_bwd', _o._p(bg), _o._p(obj), _o._p(hand), _o._p(mbg), _o._p(mh), _o._p(dimg.contiguous()), _o._p(dbg), _o._p(dobj),
-             _o._p(dhand), _o._p(dmbg), _o._p(dmh), npix, C, _o._st())
+        L.call('hoig_compose_bwd', _p(bg), _p(obj), _p(hand), _p(mbg), _p(mh), _p(dimg.contiguous()), _p(dbg), _p(dobj),
+               _p(dhand), _p(dmbg), _p(dmh), npix, C, _st())
         return dbg, dobj, dhand, dmbg, dmh
 
 
@@ -76,7 +72,7 @@ class _LossRoot(Function):
     @staticmethod
     def forward(ctx, slots, *handles):
         k = len(slots.names)
-        call('hoig_sum', _o._p(slots.buf), slots.buf.data_ptr() + 4 * k, k, _o._st())
+        L.call('hoig_sum', _p(slots.buf), slots.buf.data_ptr() + 4 * k, k, _st())
         ctx.one, ctx.n = slots.one, len(handles)
         return slots.buf[k]
 
@@ -91,7 +87,7 @@ class _MeanLoss(Function):
 
     @staticmethod
     def forward(ctx, pred, target, kind, tconst, scale, into=None):
-        _o._chk(pred); _o._chk(target)
+        _chk(pred); _chk(target)
         pred = pred.contiguous()
         n = pred.numel()
         need = pred.requires_grad
@@ -100,11 +96,11 @@ class _MeanLoss(Function):
         ctx.term = into is not None
         if into is not None:
             slots, k = into
-            call('hoig_loss_accumulate', kind, _o._p(pred), _o._p(target), tconst, scale / n, slots.buf.data_ptr() + 4 * k, _o._p(dpred), n,
-                 _o._st())
+            L.call('hoig_loss_accumulate', kind, _p(pred), _p(target), tconst, scale / n, slots.buf.data_ptr() + 4 * k, _p(dpred), n,
+                   _st())
             return slots.buf[k]
         out = torch.zeros(1, dtype=torch.float32, device=pred.device)
-        call('hoig_loss_fwd_bwd', kind, _o._p(pred), _o._p(target), tconst, scale / n, _o._p(out), _o._p(dpred), n, _o._st())
+        L.call('hoig_loss_fwd_bwd', kind, _p(pred), _p(target), tconst, scale / n, _p(out), _p(dpred), n, _st())
         return out[0] * (scale / n)
 
     @staticmethod
@@ -137,7 +133,7 @@ class _TV(Function):
 
     @staticmethod
     def forward(ctx, m, scale, into=None):
-        _o._chk(m)
+        _chk(m)
         m = m.contiguous()
         B, H, W, C = m.shape
         assert C == 1
@@ -148,10 +144,10 @@ class _TV(Function):
         ctx.term = into is not None
         if into is not None:                  # a term of an objective: see LossSlots
             slots, k = into
-            call('hoig_tv_accumulate', _o._p(m), scale / nx, scale / ny, slots.buf.data_ptr() + 4 * k, _o._p(dm), B, H, W, _o._st())
+            L.call('hoig_tv_accumulate', _p(m), scale / nx, scale / ny, slots.buf.data_ptr() + 4 * k, _p(dm), B, H, W, _st())
             return slots.buf[k]
         out = torch.zeros(2, dtype=torch.float32, device=m.device)
-        call('hoig_tv_fwd_bwd', _o._p(m), scale / nx, scale / ny, _o._p(out), _o._p(dm), B, H, W, _o._st())
+        L.call('hoig_tv_fwd_bwd', _p(m), scale / nx, scale / ny, _p(out), _p(dm), B, H, W, _st())
         return out[0] * (scale / nx) + out[1] * (scale / ny)
 
     @staticmethod
@@ -170,10 +166,10 @@ def mean(x, into=None):
     """into = LossSlots.term(name) of a report-only slot: the mean is added there (no result tensor)."""
     if into is not None:
         slots, k = into
-        call('hoig_sum_scaled', _o._p(x.contiguous()), 1.0 / x.numel(), slots.buf.data_ptr() + 4 * k, x.numel(), _o._st())
+        L.call('hoig_sum_scaled', _p(x.contiguous()), 1.0 / x.numel(), slots.buf.data_ptr() + 4 * k, x.numel(), _st())
         return slots.buf[k]
     out = torch.zeros(1, dtype=torch.float32, device=x.device)
-    call('hoig_sum', _o._p(x.contiguous()), _o._p(out), x.numel(), _o._st())
+    L.call('hoig_sum', _p(x.contiguous()), _p(out), x.numel(), _st())
     return out[0] / x.numel()
 
 
@@ -183,5 +179,5 @@ def tensor2im_u8(x_nhwc, nrow, unnormalize=True):
     ncol = min(nrow, B)
     nrw = (B + ncol - 1) // ncol
     out = torch.empty((C, nrw * H, ncol * W), dtype=torch.uint8, device=x_nhwc.device)
-    call('hoig_tensor2im_u8', _o._p(x_nhwc.contiguous()), _o._p(out), B, H, W, C, nrow, 1 if unnormalize else 0, _o._st())
+    L.call('hoig_tensor2im_u8', _p(x_nhwc.contiguous()), _p(out), B, H, W, C, nrow, 1 if unnormalize else 0, _st())
     return out

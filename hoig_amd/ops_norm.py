@@ -1,13 +1,11 @@
 """Instance / SPADE normalisation operators (split off hoig_amd/ops.py in round 6; re-exported there: `ops.instance_norm`, ...)."""
 import contextlib
-import ctypes
 
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from ._lib import call, ConvDesc
-from . import ops as _o          # (names of the core module are read at call time: _chk, _claim_split, _grad_epoch, _grad_target, _offer_split, _p, _st, _writes_split)
+from .ops import _chk, _claim_split, _grad_epoch, _grad_target, _offer_split, _p, _st, _writes_split
 
 # ------------------------------------------------------------------------------------------------- instance norm
 _norm_ws = {}
@@ -75,7 +73,7 @@ def _stats_offer(y):
 class _INorm(Function):
     @staticmethod
     def forward(ctx, x, p0, p1, mode, act, slope, residual, eps):
-        _o._chk(x, 'x')
+        _chk(x, 'x')
         assert x.is_contiguous()
         B, H, W, C = x.shape
         HW = H * W
@@ -85,20 +83,17 @@ class _INorm(Function):
         rstd = torch.empty_like(mean)
         y = torch.empty_like(x)
         # maps of <= 1024 pixels: statistics + apply in one launch from one read of x
-        rc = L.EUNSUPPORTED if HW > 1024 else L.lib.hoig_inorm_fwd_fused(_o._p(x), mode, _o._p(p0), _o._p(p1), C, act, slope, _o._p(residual),
-                                                                         eps, _o._p(y), _o._p(mean), _o._p(rstd), B, HW, C, _o._st())
-        if rc == L.EUNSUPPORTED:
+        if HW > 1024 or not L.attempt('hoig_inorm_fwd_fused', _p(x), mode, _p(p0), _p(p1), C, act, slope, _p(residual), eps, _p(y), _p(mean),
+                                      _p(rstd), B, HW, C, _st()):
             ws, have = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device, take=(x.data_ptr(), B, HW, C))
             if have:              # the convolution that made x left its sums in the accumulators: no pass over x for them
-                call('hoig_inorm_stats_from_sums', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
+                L.call('hoig_inorm_stats_from_sums', _p(x), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
             else:
-                call('hoig_inorm_stats', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
-            call('hoig_inorm_apply', _o._p(x), _o._p(mean), _o._p(rstd), mode, _o._p(p0), _o._p(p1), act, slope, _o._p(residual), _o._p(y),
-                 B, HW, C, _o._st())
-        else:
-            L.check(rc, 'hoig_inorm_fwd_fused')
+                L.call('hoig_inorm_stats', _p(x), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
+            L.call('hoig_inorm_apply', _p(x), _p(mean), _p(rstd), mode, _p(p0), _p(p1), act, slope, _p(residual), _p(y),
+                   B, HW, C, _st())
         ctx.cfg = (mode, act, slope, B, HW, C, residual is not None)
-        ctx.split_tok = _o._claim_split(x)          # x is the output of a convolution whose backward reads split dy
+        ctx.split_tok = _claim_split(x)          # x is the output of a convolution whose backward reads split dy
         # (Leaky)ReLU after a plain / affine norm: the backward recomputes the activation mask from x instead of reading y
         y_free = act in (L.ACT_RELU, L.ACT_LRELU) and mode in (0, 1)
         ctx.save_for_backward(x, mean, rstd, p0, p1, y if (act != L.ACT_NONE and not y_free) else None)
@@ -106,32 +101,29 @@ class _INorm(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _o._grad_epoch()
+        _grad_epoch()
         x, mean, rstd, p0, p1, y = ctx.saved_tensors
         mode, act, slope, B, HW, C, has_res = ctx.cfg
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dp0 = dp1 = r0 = r1 = None
         if mode == 1:
-            dp0, ret0 = _o._grad_target(p0)
-            dp1, ret1 = _o._grad_target(p1)
+            dp0, ret0 = _grad_target(p0)
+            dp1, ret1 = _grad_target(p1)
             r0, r1 = (dp0 if ret0 else None), (dp1 if ret1 else None)
         elif mode == 2:
             dp0, dp1 = torch.empty_like(x), torch.empty_like(x)
             r0, r1 = dp0, dp1
-        split_dx = _o._writes_split(ctx.split_tok)
+        split_dx = _writes_split(ctx.split_tok)
         sfx = '_split' if split_dx else ''
-        p1m = _o._p(p1) if mode == 1 else None
-        rc = getattr(L.lib, 'hoig_inorm_bwd_fused_add' + sfx)(_o._p(x), _o._p(mean), _o._p(rstd), mode, _o._p(p0), p1m, C, _o._p(y), _o._p(dy), act, slope,
-                                                              None, _o._p(dx), _o._p(dp0), _o._p(dp1), B, HW, C, _o._st())
-        if rc == L.EUNSUPPORTED:
+        p1m = _p(p1) if mode == 1 else None
+        if not L.attempt('hoig_inorm_bwd_fused_add' + sfx, _p(x), _p(mean), _p(rstd), mode, _p(p0), p1m, C, _p(y), _p(dy), act, slope, None, _p(dx),
+                         _p(dp0), _p(dp1), B, HW, C, _st()):
             ws = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device)
-            call('hoig_inorm_bwd_add_ld' + sfx, _o._p(x), _o._p(mean), _o._p(rstd), mode, _o._p(p0), p1m, C, _o._p(y), _o._p(dy), act, slope, None, _o._p(dx),
-                 _o._p(dp0), _o._p(dp1), B, HW, C, _o._p(ws), _o._st())
-        else:
-            L.check(rc, 'hoig_inorm_bwd_fused_add' + sfx)
+            L.call('hoig_inorm_bwd_add_ld' + sfx, _p(x), _p(mean), _p(rstd), mode, _p(p0), p1m, C, _p(y), _p(dy), act, slope, None, _p(dx),
+                   _p(dp0), _p(dp1), B, HW, C, _p(ws), _st())
         if split_dx:
-            _o._offer_split(ctx.split_tok, dx)
+            _offer_split(ctx.split_tok, dx)
         return dx, r0, r1, None, None, None, (dy if has_res else None), None
 
 
@@ -151,7 +143,7 @@ class _SpadeFused(Function):
 
     @staticmethod
     def forward(ctx, x, gb, act, slope, eps, fork=False):
-        _o._chk(x); _o._chk(gb)
+        _chk(x); _chk(gb)
         assert x.is_contiguous() and gb.is_contiguous()
         B, H, W, C = x.shape
         assert gb.shape[-1] == 2 * C
@@ -159,20 +151,17 @@ class _SpadeFused(Function):
         mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         y = torch.empty_like(x)
-        rc = L.EUNSUPPORTED if HW > 1024 else L.lib.hoig_inorm_fwd_fused(_o._p(x), 2, _o._p(gb), gb.data_ptr() + 4 * C, 2 * C, act, slope,
-                                                                         None, eps, _o._p(y), _o._p(mean), _o._p(rstd), B, HW, C, _o._st())
-        if rc == L.EUNSUPPORTED:
+        if HW > 1024 or not L.attempt('hoig_inorm_fwd_fused', _p(x), 2, _p(gb), gb.data_ptr() + 4 * C, 2 * C, act, slope, None, eps, _p(y),
+                                      _p(mean), _p(rstd), B, HW, C, _st()):
             ws, have = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device, take=(x.data_ptr(), B, HW, C))
             if have:
-                call('hoig_inorm_stats_from_sums', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
+                L.call('hoig_inorm_stats_from_sums', _p(x), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
             else:
-                call('hoig_inorm_stats', _o._p(x), B, HW, C, eps, _o._p(mean), _o._p(rstd), _o._p(ws), _o._st())
-            call('hoig_inorm_apply_ld', _o._p(x), _o._p(mean), _o._p(rstd), 2, _o._p(gb), gb.data_ptr() + 4 * C, 2 * C, act, slope, None,
-                 _o._p(y), B, HW, C, _o._st())
-        else:
-            L.check(rc, 'hoig_inorm_fwd_fused')
+                L.call('hoig_inorm_stats', _p(x), B, HW, C, eps, _p(mean), _p(rstd), _p(ws), _st())
+            L.call('hoig_inorm_apply_ld', _p(x), _p(mean), _p(rstd), 2, _p(gb), gb.data_ptr() + 4 * C, 2 * C, act, slope, None,
+                   _p(y), B, HW, C, _st())
         ctx.cfg = (act, slope, B, HW, C)
-        ctx.split_tok = _o._claim_split(x)          # (see _INorm.forward)
+        ctx.split_tok = _claim_split(x)          # (see _INorm.forward)
         ctx.save_for_backward(x, mean, rstd, gb, y if act != L.ACT_NONE else None)
         if fork:                              # (y, x): see _Conv.forward
             ctx.set_materialize_grads(False)
@@ -189,18 +178,15 @@ class _SpadeFused(Function):
         add = dxr.contiguous() if dxr is not None else None
         dx = torch.empty_like(x)
         dgb = torch.empty_like(gb)
-        split_dx = _o._writes_split(ctx.split_tok)
+        split_dx = _writes_split(ctx.split_tok)
         sfx = '_split' if split_dx else ''
-        rc = getattr(L.lib, 'hoig_inorm_bwd_fused_add' + sfx)(_o._p(x), _o._p(mean), _o._p(rstd), 2, _o._p(gb), None, 2 * C, _o._p(y), _o._p(dy), act, slope,
-                                                              _o._p(add), _o._p(dx), _o._p(dgb), dgb.data_ptr() + 4 * C, B, HW, C, _o._st())
-        if rc == L.EUNSUPPORTED:
+        if not L.attempt('hoig_inorm_bwd_fused_add' + sfx, _p(x), _p(mean), _p(rstd), 2, _p(gb), None, 2 * C, _p(y), _p(dy), act, slope, _p(add),
+                         _p(dx), _p(dgb), dgb.data_ptr() + 4 * C, B, HW, C, _st()):
             ws = _norm_workspace(L.lib.hoig_inorm_workspace_bytes(B, HW, C) // 4, x.device)
-            call('hoig_inorm_bwd_add_ld' + sfx, _o._p(x), _o._p(mean), _o._p(rstd), 2, _o._p(gb), None, 2 * C, _o._p(y), _o._p(dy), act, slope, _o._p(add),
-                 _o._p(dx), _o._p(dgb), dgb.data_ptr() + 4 * C, B, HW, C, _o._p(ws), _o._st())
-        else:
-            L.check(rc, 'hoig_inorm_bwd_fused_add' + sfx)
+            L.call('hoig_inorm_bwd_add_ld' + sfx, _p(x), _p(mean), _p(rstd), 2, _p(gb), None, 2 * C, _p(y), _p(dy), act, slope, _p(add),
+                   _p(dx), _p(dgb), dgb.data_ptr() + 4 * C, B, HW, C, _p(ws), _st())
         if split_dx:
-            _o._offer_split(ctx.split_tok, dx)
+            _offer_split(ctx.split_tok, dx)
         return dx, dgb, None, None, None, None
 
 

@@ -1,22 +1,19 @@
 """Element-wise, channel-bookkeeping and sampling operators (split off hoig_amd/ops.py in round 6; re-exported there)."""
-import contextlib
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from ._lib import call, ConvDesc
-from . import ops as _o          # (names of the core module are read at call time: _chk, _p, _st, conv2d, packed_strides, precision)
+from . import ops as _o          # (ops.precision is rebound at run time, see ops._reexport; ops.conv2d is read where it is called)
+from .ops import _chk, _p, _st, packed_strides
 
 # ------------------------------------------------------------------------------------------------- small ops
 class _Add(Function):
     @staticmethod
     def forward(ctx, a, b):
-        _o._chk(a); _o._chk(b)
+        _chk(a); _chk(b)
         assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
         y = torch.empty_like(a)
-        call('hoig_add', _o._p(a), _o._p(b), _o._p(y), a.numel(), _o._st())
+        L.call('hoig_add', _p(a), _p(b), _p(y), a.numel(), _st())
         return y
 
     @staticmethod
@@ -33,10 +30,10 @@ class _AddAct(Function):
 
     @staticmethod
     def forward(ctx, a, b, act, slope):
-        _o._chk(a); _o._chk(b)
+        _chk(a); _chk(b)
         assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
         y = torch.empty_like(a)
-        call('hoig_add_act', _o._p(a), _o._p(b), _o._p(y), act, slope, a.numel(), _o._st())
+        L.call('hoig_add_act', _p(a), _p(b), _p(y), act, slope, a.numel(), _st())
         ctx.cfg = (act, slope)
         ctx.save_for_backward(y)
         return y
@@ -46,7 +43,7 @@ class _AddAct(Function):
         y, = ctx.saved_tensors
         act, slope = ctx.cfg
         g = torch.empty_like(y)
-        call('hoig_act_bwd', _o._p(y), _o._p(dy.contiguous()), _o._p(g), act, slope, y.numel(), _o._st())
+        L.call('hoig_act_bwd', _p(y), _p(dy.contiguous()), _p(g), act, slope, y.numel(), _st())
         return g, g, None, None
 
 
@@ -56,20 +53,20 @@ def add_act(a, b, act, slope=0.0):
 
 def _copy_channels(x, y, x_off, y_off, n, accumulate=False):
     npix = x.numel() // x.shape[-1]
-    call('hoig_copy_channels', _o._p(x), _o._p(y), npix, x.shape[-1], x_off, y.shape[-1], y_off, n, 1 if accumulate else 0,
-         _o._st())
+    L.call('hoig_copy_channels', _p(x), _p(y), npix, x.shape[-1], x_off, y.shape[-1], y_off, n, 1 if accumulate else 0,
+           _st())
 
 
 class _Cat(Function):
     @staticmethod
     def forward(ctx, *xs):
         for t in xs:
-            _o._chk(t)
+            _chk(t)
             assert t.is_contiguous()
         cs = [t.shape[-1] for t in xs]
         y = torch.empty(xs[0].shape[:-1] + (sum(cs),), dtype=xs[0].dtype, device=xs[0].device)
         if len(xs) == 2:
-            call('hoig_cat2_channels', _o._p(xs[0]), cs[0], _o._p(xs[1]), cs[1], _o._p(y), y.numel() // y.shape[-1], _o._st())
+            L.call('hoig_cat2_channels', _p(xs[0]), cs[0], _p(xs[1]), cs[1], _p(y), y.numel() // y.shape[-1], _st())
         else:
             off = 0
             for t, c in zip(xs, cs):
@@ -104,7 +101,7 @@ class _PadChannels(Function):
 
     @staticmethod
     def forward(ctx, x, c_to):
-        _o._chk(x)
+        _chk(x)
         assert x.is_contiguous() and c_to > x.shape[-1]
         y = torch.zeros(x.shape[:-1] + (c_to,), dtype=x.dtype, device=x.device)
         _copy_channels(x, y, 0, 0, x.shape[-1])
@@ -123,8 +120,8 @@ class _PadConvIn(Function):
     @staticmethod
     def forward(ctx, w, c_to):
         co, ci, r, s_ = w.shape
-        assert tuple(w.stride()) == _o.packed_strides(w.shape, False) and c_to > ci
-        out = torch.empty_strided((co, c_to, r, s_), _o.packed_strides((co, c_to, r, s_), False), dtype=w.dtype, device=w.device)
+        assert tuple(w.stride()) == packed_strides(w.shape, False) and c_to > ci
+        out = torch.empty_strided((co, c_to, r, s_), packed_strides((co, c_to, r, s_), False), dtype=w.dtype, device=w.device)
         out.zero_()
         out[:, :ci].copy_(w)
         ctx.ci = ci
@@ -153,30 +150,30 @@ def slice_channels(x, a, b):
 
 
 def nchw_to_nhwc(x):
-    _o._chk(x)
+    _chk(x)
     x = x.contiguous()
     B, C, H, W = x.shape
     y = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device)
-    call('hoig_nchw_to_nhwc', _o._p(x), _o._p(y), B, C, H, W, _o._st())
+    L.call('hoig_nchw_to_nhwc', _p(x), _p(y), B, C, H, W, _st())
     return y
 
 
 def nhwc_to_nchw(x):
-    _o._chk(x)
+    _chk(x)
     x = x.contiguous()
     B, H, W, C = x.shape
     y = torch.empty((B, C, H, W), dtype=x.dtype, device=x.device)
-    call('hoig_nhwc_to_nchw', _o._p(x), _o._p(y), B, C, H, W, _o._st())
+    L.call('hoig_nhwc_to_nchw', _p(x), _p(y), B, C, H, W, _st())
     return y
 
 
 class _MaxPool(Function):
     @staticmethod
     def forward(ctx, x):
-        _o._chk(x)
+        _chk(x)
         B, H, W, C = x.shape
         y = torch.empty((B, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
-        call('hoig_maxpool2_fwd', _o._p(x), _o._p(y), B, H, W, C, _o._st())
+        L.call('hoig_maxpool2_fwd', _p(x), _p(y), B, H, W, C, _st())
         ctx.save_for_backward(x)
         return y
 
@@ -185,7 +182,7 @@ class _MaxPool(Function):
         x, = ctx.saved_tensors
         B, H, W, C = x.shape
         dx = torch.empty_like(x)
-        call('hoig_maxpool2_bwd', _o._p(x), None, _o._p(dy.contiguous()), _o._p(dx), B, H, W, C, _o._st())
+        L.call('hoig_maxpool2_bwd', _p(x), None, _p(dy.contiguous()), _p(dx), B, H, W, C, _st())
         return dx
 
 
@@ -197,7 +194,7 @@ def maxpool2(x):
 def resize_bilinear_ac(x, ho, wo):
     B, Hi, Wi, C = x.shape
     y = torch.empty((B, ho, wo, C), dtype=x.dtype, device=x.device)
-    call('hoig_resize_bilinear_ac', _o._p(x.contiguous()), _o._p(y), B, Hi, Wi, C, ho, wo, _o._st())
+    L.call('hoig_resize_bilinear_ac', _p(x.contiguous()), _p(y), B, Hi, Wi, C, ho, wo, _st())
     return y
 
 
@@ -206,25 +203,25 @@ def resize_nearest(x, ho, wo):
     if (Hi, Wi) == (ho, wo):
         return x
     y = torch.empty((B, ho, wo, C), dtype=x.dtype, device=x.device)
-    call('hoig_resize_nearest', _o._p(x.contiguous()), _o._p(y), B, Hi, Wi, C, ho, wo, _o._st())
+    L.call('hoig_resize_nearest', _p(x.contiguous()), _p(y), B, Hi, Wi, C, ho, wo, _st())
     return y
 
 
 def attn_flow(tscale):
     B, h = tscale.shape[0], tscale.shape[1]
     flow = torch.empty((B, 2, h, h), dtype=tscale.dtype, device=tscale.device)
-    call('hoig_attn_flow', _o._p(tscale.contiguous()), _o._p(flow), B, h, _o._st())
+    L.call('hoig_attn_flow', _p(tscale.contiguous()), _p(flow), B, h, _st())
     return flow
 
 
 class _GridSample(Function):
     @staticmethod
     def forward(ctx, x, grid):
-        _o._chk(x); _o._chk(grid)
+        _chk(x); _chk(grid)
         B, H, W, C = x.shape
         Ho, Wo = grid.shape[1], grid.shape[2]
         y = torch.empty((B, Ho, Wo, C), dtype=x.dtype, device=x.device)
-        call('hoig_grid_sample_fwd', _o._p(x), _o._p(grid), _o._p(y), B, H, W, C, Ho, Wo, _o._st())
+        L.call('hoig_grid_sample_fwd', _p(x), _p(grid), _p(y), B, H, W, C, Ho, Wo, _st())
         ctx.save_for_backward(grid)
         ctx.shape = (B, H, W, C, Ho, Wo)
         return y
@@ -234,12 +231,10 @@ class _GridSample(Function):
         grid, = ctx.saved_tensors
         B, H, W, C, Ho, Wo = ctx.shape
         dx = torch.zeros((B, H, W, C), dtype=dy.dtype, device=dy.device)
-        call('hoig_grid_sample_bwd', _o._p(grid), _o._p(dy.contiguous()), _o._p(dx), B, H, W, C, Ho, Wo, _o._st())
+        L.call('hoig_grid_sample_bwd', _p(grid), _p(dy.contiguous()), _p(dx), B, H, W, C, Ho, Wo, _st())
         return dx, None
 
 
 def grid_sample(x, grid):
     return _GridSample.apply(x, grid.contiguous())
 
-
-_f6_cache = {}

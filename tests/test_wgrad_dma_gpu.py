@@ -374,3 +374,75 @@ def test_grouped_backward_skips_the_weight_gradient_of_a_frozen_weight():
     finally:
         L.set_tuning('pair', prev)
         ops.set_precision('f32')
+
+
+def _conv_norm_chain():
+    from hoig_amd import _lib as L, ops
+    tree, x, y, g = _tagged_conv()
+    gout = torch.randn(y.shape, device='cuda', generator=g)
+    (ops.instance_norm(y, act=L.ACT_RELU) * gout).sum().backward()
+    return [x.grad], [tree.flat_grad]
+
+
+def _grouped_pair_chain():
+    """(the set-up of test_grouped_backward_skips_the_weight_gradient_of_a_frozen_weight, both weights live)"""
+    from hoig_amd import _lib as L, nn as hnn, ops
+    prev = L.set_tuning('pair', 1)
+    try:
+        g = torch.Generator(device='cuda').manual_seed(23)
+        tree = hnn.ParamTree({'a.weight': (256, 64, 3, 3), 'b.weight': (256, 64, 3, 3)}, torch.device('cuda'), {}, {})
+        with torch.no_grad():
+            tree.flat.copy_(torch.randn(tree.flat.shape, device='cuda', generator=g) * 0.05)
+        tree.version += 1
+        xa, xb = (torch.randn(8, 32, 32, 64, device='cuda', generator=g).requires_grad_(True) for _ in range(2))
+        ga, gb = (torch.randn(8, 32, 32, 256, device='cuda', generator=g) for _ in range(2))
+        wa, wb = tree.P['a.weight'], tree.P['b.weight']
+        assert ops.pair_ok(xa, xb, wa, wb)
+        ya, yb = ops.conv2d_pair(xa, xb, wa, wb)
+        ((ya * ga).sum() + (yb * gb).sum()).backward()
+        return [xa.grad, xb.grad], [wa.grad, wb.grad]
+    finally:
+        L.set_tuning('pair', prev)
+
+
+@pytest.mark.parametrize('chain', [_conv_norm_chain, _grouped_pair_chain])
+def test_a_refused_pre_split_weight_gradient_unsplits_on_the_side_stream(chain):
+    """The innermost fallback of the backward: the pre-split weight-gradient entry points REFUSE (every tagged shape of this file is one
+    they accept, so the refusal is forced), the backward un-splits dy on the weight-gradient side stream, runs hoig_conv2d_bwd_weight
+    on the copy and holds it until that launch has run, and the data gradient does not use a copy made on the other stream.  Same
+    arithmetic as the accepted path: dx to the un-split-against-pre-split bound of this file, dW to the order of the fp32 atomics
+    (H * W <= 1024: no statistics from an epilogue)."""
+    from hoig_amd import _lib as L, ops
+    names = ('hoig_conv2d_bwd_weight_split', 'hoig_conv2d_bwd_weight_split_pair')
+    real = {n: getattr(L.lib, n) for n in names}
+    refusals = []
+
+    def refuse(*args):
+        refusals.append(len(args))
+        return L.EUNSUPPORTED
+    ops.set_precision('bf16x3:f16x2')
+    try:
+        res = []
+        for forced in (False, True):
+            if forced:
+                for n in names:
+                    setattr(L.lib, n, refuse)          # (an instance attribute shadows the CDLL's lazily bound function)
+            dxs, dws = chain()
+            ops.join_wgrad_streams()
+            ops.check_split_grads_consumed()
+            torch.cuda.synchronize()
+            res.append(([t.clone() for t in dxs], [t.clone() for t in dws]))
+            assert bool(refusals) == forced
+    finally:
+        for n in names:
+            setattr(L.lib, n, real[n])
+        ops.set_precision('f32')
+    (dx0, dw0), (dx1, dw1) = res
+    for a, b in zip(dx0, dx1):
+        err, bound = (a - b).abs().max().item(), 4e-6 * a.abs().max().item()
+        print('dx: max |diff| %.3g, bound %.3g' % (err, bound))
+        assert err <= bound, (err, bound)
+    for a, b in zip(dw0, dw1):
+        rel = ((a - b).norm() / a.norm()).item()
+        print('dW: relative difference %.3g, bound 2e-5' % rel)
+        assert a.abs().max().item() > 0 and rel < 2e-5, rel

@@ -2,7 +2,6 @@
 calls, time, TFLOP/s.  Each launch is bracketed by events (this serialises nothing: one stream), so the sum matches the
 kernel-trace view.  Usage: python tools/conv_table.py [precision] [batch] [side]"""
 import collections
-import ctypes
 import os
 import sys
 
@@ -39,7 +38,11 @@ def timed(kind, d, fn):
     return r
 
 
-_fwd, _dgrad, _call = ops._conv_fwd_raw, ops._conv_dgrad_raw, ops.call
+_fwd, _dgrad, _call, _attempt = ops._conv_fwd_raw, ops._conv_dgrad_raw, L.call, L.attempt
+# (the launches that do not pass through the two functions above: weight gradients, the pre-split forms, ops.conv2d_cat2's own)
+_KIND = {'hoig_conv2d_bwd_weight': 'wgrad', 'hoig_conv2d_bwd_weight_split': 'wgrad', 'hoig_conv2d_bwd_data_packed_split': 'dgrad',
+         'hoig_conv2d_cat_fwd_packed_stats': 'fwd', 'hoig_conv2d_cat_fwd_packed': 'fwd', 'hoig_conv2d_cat_bwd_data_packed': 'dgrad',
+         'hoig_conv2d_cat_bwd_weight': 'wgrad'}
 
 
 def fwd(d, *a, **k):
@@ -51,27 +54,22 @@ def dgrad(d, *a, **k):
 
 
 def call(name, *a):
-    if name == 'hoig_conv2d_bwd_weight':
-        d = a[0]._obj
-        return timed('wgrad', d, lambda: _call(name, *a))
+    if name in _KIND:
+        return timed(_KIND[name], a[0]._obj, lambda: _call(name, *a))
     return _call(name, *a)
 
 
-ops._conv_fwd_raw, ops._conv_dgrad_raw, ops.call = fwd, dgrad, call
+def attempt(name, *a):
+    """(the pre-split entry points; a refused attempt launched nothing: its record is taken back)"""
+    if name not in _KIND or not enabled[0]:
+        return _attempt(name, *a)
+    ok = timed(_KIND[name], a[0]._obj, lambda: _attempt(name, *a))
+    if not ok:
+        records.pop()
+    return ok
 
 
-def wrap_lib(name, kind):
-    """the pre-split entry points are called through L.lib directly (ops._Conv._backward_split): time them too"""
-    orig = getattr(L.lib, name)
-
-    def f(dref, *a):
-        return timed(kind, dref._obj, lambda: orig(dref, *a))
-    setattr(L.lib, name, f)
-
-
-from hoig_amd import _lib as L          # noqa: E402
-wrap_lib('hoig_conv2d_bwd_weight_split', 'wgrad')
-wrap_lib('hoig_conv2d_bwd_data_packed_split', 'dgrad')
+ops._conv_fwd_raw, ops._conv_dgrad_raw, L.call, L.attempt = fwd, dgrad, call, attempt
 
 opt = opt_namespace(gen_name='generator_spade_attn', local_rank=0, image_size=side, hip_graph=False)
 torch.manual_seed(8)

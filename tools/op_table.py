@@ -1,7 +1,6 @@
 """Per-entry-point / per-shape table of EVERY C-ABI launch of one training step (name, integer arguments, calls, time).
 Usage: python tools/op_table.py [precision] [batch] [side] [name filter]"""
 import collections
-import ctypes
 import os
 import sys
 
@@ -10,7 +9,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from hoig_amd import ops, nn as hnn, synthetic, _lib as L   # noqa: E402
+from hoig_amd import ops, synthetic, _lib as L          # noqa: E402
 from hoig_amd.models import ModelsFactory               # noqa: E402
 from common import opt_namespace                        # noqa: E402
 
@@ -21,7 +20,7 @@ filt = sys.argv[4] if len(sys.argv) > 4 else ''
 ops.set_precision(prec)
 records = []
 enabled = [False]
-_call = L.call
+_call, _attempt = L.call, L.attempt
 
 
 def sig(a):
@@ -38,20 +37,22 @@ def sig(a):
     return tuple(out)
 
 
-def call(name, *a):
-    if not enabled[0]:
-        return _call(name, *a)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    r = _call(name, *a)
-    e1.record()
-    records.append((name, sig(a), e0, e1))
-    return r
+def timed(fn):
+    """fn = L.call | L.attempt; an attempt the entry point refused launched nothing and is not listed"""
+    def f(name, *a):
+        if not enabled[0]:
+            return fn(name, *a)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn(name, *a)
+        e1.record()
+        if r is not False:
+            records.append((name, sig(a), e0, e1))
+        return r
+    return f
 
 
-for mod in (ops, hnn, L):
-    if getattr(mod, 'call', None) is _call:
-        mod.call = call
+L.call, L.attempt = timed(_call), timed(_attempt)       # every module launches through these two names, read at call time
 
 opt = opt_namespace(gen_name='generator_spade_attn', local_rank=0, image_size=side)
 torch.manual_seed(8)
