@@ -18,6 +18,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16X2, PREC_F16F6 = 0, 1, 2, 3, 4
 LOSS_L1, LOSS_MSE, LOSS_BCE = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
+JPEG_SUBSEQ_BYTES = 64              # HOIG_JPEG_SUBSEQ_BYTES
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
 
 
@@ -156,6 +157,8 @@ _SIGS = {
     'hoig_jpeg_entropy_host': [_vp, _i64, _vp, _i, _vp, _i64, _vp, _i64, _vp],
     'hoig_jpeg_decode_bgr_u8': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp],
     'hoig_jpeg_reconstruct_bgr_u8': [_vp, _vp, _i, _vp, _i64, _vp, _i64, _vp],
+    'hoig_jpeg_entropy_par_host': [_vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64],
+    'hoig_jpeg_decode_bgr_u8_par': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp],
 }
 
 
@@ -193,6 +196,8 @@ def _load():
     lib.hoig_ssim_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]
+    lib.hoig_jpeg_decode_par_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_version.argtypes = []
     lib.hoig_version.restype = ctypes.c_char_p
     return lib

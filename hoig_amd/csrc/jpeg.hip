@@ -1,5 +1,5 @@
 // JPEG frames decoded on the device (the loader's rgb/*.jpg and color_%06d.jpg; include/hoig_kernels.h has the interface, DESIGN.md
-// section 10 the rules).  Three kernels per batch:
+// section 10 the rules).  Three kernels per batch (five launches with the parallel entropy stage):
 //
 //   jpeg_entropy_kernel   Huffman decode.  Serial inside a restart interval by nature (a code's position depends on every code before
 //                         it), so one workgroup of ONE wave takes an (image, interval) pair: lanes 0-5 build the image's lookup tables in
@@ -7,6 +7,15 @@
 //                         runs on the CPU -- while the whole wave feeds it: the stream comes through a 4 KB LDS window that all 64 lanes
 //                         refill with 16-byte loads (a byte at a time from global memory would cost a round trip per byte), and each
 //                         finished block leaves as one 128-byte row, zeros included, so the coefficient buffer needs no clearing.
+//   jpeg_entropy_par_kernel  (hoig_jpeg_decode_bgr_u8_par, instead of the kernel above) Huffman decode that is parallel INSIDE an interval:
+//                         jpeg_parallel.h's self-synchronising sub-sequences.  One workgroup of 128 / 256 / 512 threads (sub-sequences
+//                         of 256 / 128 / 32-64 bytes) takes an (image, interval) pair and walks it in chunks of at most 32 KB, which all
+//                         threads stage in LDS with 16-byte loads (a dword of padding behind every sub-sequence keeps neighbouring
+//                         lanes in different banks); the lanes' states, block counts and DC sums live in LDS; rounds are separated by
+//                         workgroup barriers with an "anything changed" vote, and only lanes whose state changed decode again.  The
+//                         coefficients are zeroed by one memset in front of it (a lane that starts inside a block continues it).
+//   jpeg_entropy_flagged_kernel  the serial kernel again, for the intervals the parallel one found irregular (corrupt streams): it
+//                         writes their blocks and the status word; every other workgroup ends at once.
 //   jpeg_idct_kernel      dequantise + jidctint's islow IDCT, one thread per 8 x 8 block, into padded uint8 component planes.
 //   jpeg_colour_kernel    libjpeg's fancy upsampling (h2v1 / h2v2 triangle filters) and fixed-point YCbCr -> RGB, one thread per pixel,
 //                         written as interleaved BGR.
@@ -15,6 +24,7 @@
 // image's status word and stops; nothing is read or written outside the buffers the plans describe (the entry points check the plans).
 #include "common.h"
 #include "jpeg_entropy.h"
+#include "jpeg_parallel.h"
 
 namespace {
 
@@ -64,6 +74,109 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t *__restr
     const hoig_jpeg_plan &P = plans[img];
     if (iv >= P.n_intervals) return;
     __shared__ JpegHuff tab[6];                      // DC of components 0-2, then AC
+    __shared__ __attribute__((aligned(16))) uint8_t win[WIN];
+    __shared__ int16_t blk[64];
+    bool ok = true;
+    if (lane < 6 && lane % 3 < P.ncomp) {
+        const int c = lane % 3;
+        ok = lane < 3 ? jpeg_build_huff(P.dc_counts[c], P.dc_vals[c], 16, &tab[lane]) : jpeg_build_huff(P.ac_counts[c], P.ac_vals[c], 256, &tab[lane]);
+    }
+    __syncthreads();
+    if (__any(!ok)) {
+        if (lane == 0) atomicOr(status + img, (int32_t)HOIG_JPEG_ECODE);
+        return;
+    }
+    DevCtx cx;
+    cx.bytes = bytes; cx.nbytes = nbytes; cx.data_off = P.data_off;
+    cx.win = win; cx.blk = blk; cx.base = -(1 << 30); cx.lane = lane; cx.natural = jpeg_natural(lane);
+    const int err = jpeg_decode_interval(P, tab, tab + 3, intervals + P.interval_first, iv,
+                                         reinterpret_cast<int16_t *>(workspace + P.coef_off), cx);
+    if (err && lane == 0) atomicOr(status + img, (int32_t)err);
+}
+
+// ---- the entropy stage, parallel inside an interval (jpeg_parallel.h)
+constexpr int PAR_CHUNK = 32768;                            // bytes of a chunk in LDS
+constexpr int PAR_W_MAX = 512;                              // threads of a workgroup = lanes of a chunk = min(PAR_W_MAX, PAR_CHUNK / S)
+constexpr int PAR_WIN = PAR_CHUNK + JPEG_PAR_OVER + 32;     // staged bytes: the chunk, what a lane reads behind it, 16-byte alignment
+constexpr int PAR_LDS = PAR_WIN + PAR_WIN / 32 * 4;         // with a dword of padding behind every S bytes (S >= 32)
+
+template <int W>
+struct DevParCtx {
+    const uint8_t *bytes;
+    int64_t nbytes, data_off;
+    uint8_t *win;
+    int base, logs, tid;
+    JpegParTab T;
+
+    // Lanes read S bytes apart: 32 dwords for S = 128, i.e. all of them in two banks.  A dword of padding behind every S bytes puts
+    // neighbouring lanes one bank apart.  (The index is clamped: a position outside the staged range reads the window's last byte.)
+    __device__ unsigned at(unsigned rel) const { return rel + ((rel >> logs) << 2); }
+    __device__ uint8_t byte(int pos) const { return win[min(at((unsigned)(pos - base)), (unsigned)(PAR_LDS - 1))]; }
+    __device__ void stage(int pos0, int pos1) {
+        __syncthreads();
+        const int64_t abs0 = (data_off + pos0) & ~(int64_t)15;
+        base = (int)(abs0 - data_off);
+        const int slots = min((int)((data_off + pos1 - abs0 + 15) >> 4), PAR_WIN / 16);
+        for (int slot = tid; slot < slots; slot += W) {
+            const int64_t a = abs0 + (int64_t)slot * 16;
+            if (a + 16 <= nbytes) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(bytes + a);
+                uint32_t *d = reinterpret_cast<uint32_t *>(win + at((unsigned)slot * 16u));     // (16 bytes never straddle a padding)
+                d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            }
+        }
+        __syncthreads();
+    }
+    __device__ int first() const { return tid; }
+    __device__ int step() const { return W; }
+    __device__ void barrier() const { __syncthreads(); }
+    __device__ bool any(bool v) const { return __syncthreads_or(v) != 0; }
+    __device__ JpegParTab *tab() { return &T; }
+};
+
+// One workgroup per (image, interval): the tables in LDS as above, the chunk's bytes and its lanes' tables in LDS, then
+// jpeg_par_interval.  irregular[interval_first + iv] = 1: jpeg_entropy_flagged_kernel decodes this interval again.
+template <int W>
+__global__ __launch_bounds__(W) void jpeg_entropy_par_kernel(const uint8_t *__restrict__ bytes, int64_t nbytes,
+                                                                 const hoig_jpeg_plan *__restrict__ plans,
+                                                                 const int32_t *__restrict__ intervals, int S, int logs,
+                                                                 int32_t *__restrict__ irregular, char *__restrict__ workspace) {
+    const int img = blockIdx.y, iv = blockIdx.x, tid = threadIdx.x;
+    const hoig_jpeg_plan &P = plans[img];
+    if (iv >= P.n_intervals) return;
+    __shared__ JpegHuff tab[6];
+    __shared__ __attribute__((aligned(16))) uint8_t win[PAR_LDS];
+    __shared__ uint32_t state[W], cand[W];
+    __shared__ int32_t dirty[W], nblk[W], dc0[W], dc1[W], dc2[W], carry[8];
+    bool ok = true;
+    if (tid < 6 && tid % 3 < P.ncomp) {
+        const int c = tid % 3;
+        ok = tid < 3 ? jpeg_build_huff(P.dc_counts[c], P.dc_vals[c], 16, &tab[tid]) : jpeg_build_huff(P.ac_counts[c], P.ac_vals[c], 256, &tab[tid]);
+    }
+    int bad = __syncthreads_or(!ok);                 // (a table that is no prefix code: the serial kernel reports it)
+    if (!bad) {
+        DevParCtx<W> cx;
+        cx.bytes = bytes; cx.nbytes = nbytes; cx.data_off = P.data_off;
+        cx.win = win; cx.base = 0; cx.logs = logs; cx.tid = tid;
+        cx.T.state = state; cx.T.cand = cand; cx.T.dirty = dirty; cx.T.nblk = nblk; cx.T.dc0 = dc0; cx.T.dc1 = dc1; cx.T.dc2 = dc2;
+        cx.T.carry = carry;
+        bad = jpeg_par_interval(P, tab, tab + 3, intervals + P.interval_first, iv, reinterpret_cast<int16_t *>(workspace + P.coef_off), S,
+                                W, cx, nullptr, nullptr);
+    }
+    if (tid == 0) irregular[P.interval_first + iv] = bad;
+}
+
+// jpeg_entropy_kernel for the intervals jpeg_entropy_par_kernel marked; every other workgroup ends at once.  (The body is that
+// kernel's, repeated: it is the pinned serial path, and stays untouched.)
+__global__ __launch_bounds__(64) void jpeg_entropy_flagged_kernel(const uint8_t *__restrict__ bytes, int64_t nbytes,
+                                                                  const hoig_jpeg_plan *__restrict__ plans,
+                                                                  const int32_t *__restrict__ intervals,
+                                                                  const int32_t *__restrict__ irregular, int32_t *__restrict__ status,
+                                                                  char *__restrict__ workspace) {
+    const int img = blockIdx.y, iv = blockIdx.x, lane = threadIdx.x;
+    const hoig_jpeg_plan &P = plans[img];
+    if (iv >= P.n_intervals || !irregular[P.interval_first + iv]) return;
+    __shared__ JpegHuff tab[6];
     __shared__ __attribute__((aligned(16))) uint8_t win[WIN];
     __shared__ int16_t blk[64];
     bool ok = true;
@@ -259,4 +372,42 @@ extern "C" int hoig_jpeg_reconstruct_bgr_u8(const hoig_jpeg_plan *plans_host, co
     const int rc = check_plans(plans_host, n, 0, 0, false, out_bytes, workspace_bytes, &d);
     if (rc != HOIG_OK) return rc;
     return reconstruct(plans_dev, n, d, out, workspace, (hipStream_t)stream);
+}
+
+extern "C" int hoig_jpeg_decode_bgr_u8_par(const uint8_t *bytes, int64_t nbytes, const hoig_jpeg_plan *plans_host,
+                                           const hoig_jpeg_plan *plans_dev, int n, const int32_t *intervals, int64_t n_entries,
+                                           uint8_t *out, int64_t out_bytes, int32_t *status, void *workspace, int64_t workspace_bytes,
+                                           int subseq_bytes, hoig_stream_t stream) {
+    if (!bytes || !plans_host || !plans_dev || !intervals || !out || !status || !workspace || n <= 0 || n > 65535) return HOIG_EINVAL;
+    if (nbytes <= 0 || nbytes % 16 || ((uintptr_t)bytes & 15) || ((uintptr_t)workspace & 15)) return HOIG_EINVAL;
+    const int S = subseq_bytes ? subseq_bytes : HOIG_JPEG_SUBSEQ_BYTES;
+    if (!jpeg_par_subseq_ok(S)) return HOIG_EINVAL;
+    BatchDims d;
+    const int rc = check_plans(plans_host, n, nbytes, n_entries, true, out_bytes, workspace_bytes, &d);
+    if (rc != HOIG_OK) return rc;
+    // the table of irregular intervals lies behind every plane, and the coefficients (zeroed here) in front of every plane
+    int64_t tables, entries, coef_end = 0, plane_first = workspace_bytes;
+    jpeg_par_tables(plans_host, n, &tables, &entries);
+    if (tables + entries * (int64_t)sizeof(int32_t) > workspace_bytes) return HOIG_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const int64_t e = plans_host[i].coef_off + jpeg_geometry(plans_host[i]).blocks * 128;
+        coef_end = e > coef_end ? e : coef_end;
+        plane_first = plans_host[i].plane_off < plane_first ? plans_host[i].plane_off : plane_first;
+    }
+    if (coef_end > plane_first) return HOIG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    char *work = static_cast<char *>(workspace);
+    int32_t *irregular = reinterpret_cast<int32_t *>(work + tables);
+    if (hipMemsetAsync(status, 0, sizeof(int32_t) * n, st) != hipSuccess) return HOIG_ELAUNCH;
+    if (hipMemsetAsync(work, 0, (size_t)coef_end, st) != hipSuccess) return HOIG_ELAUNCH;
+    int logs = 5;
+    while ((1 << logs) < S) ++logs;
+    const dim3 grid(d.max_intervals, n);
+    if (S == 256) jpeg_entropy_par_kernel<128><<<grid, 128, 0, st>>>(bytes, nbytes, plans_dev, intervals, S, logs, irregular, work);
+    else if (S == 128) jpeg_entropy_par_kernel<256><<<grid, 256, 0, st>>>(bytes, nbytes, plans_dev, intervals, S, logs, irregular, work);
+    else jpeg_entropy_par_kernel<512><<<grid, 512, 0, st>>>(bytes, nbytes, plans_dev, intervals, S, logs, irregular, work);
+    HOIG_LAUNCH_CHECK();
+    jpeg_entropy_flagged_kernel<<<dim3(d.max_intervals, n), 64, 0, st>>>(bytes, nbytes, plans_dev, intervals, irregular, status, work);
+    HOIG_LAUNCH_CHECK();
+    return reconstruct(plans_dev, n, d, out, workspace, st);
 }

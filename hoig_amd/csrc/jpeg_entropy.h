@@ -3,6 +3,8 @@
 // the DC prediction and the block loop of one restart interval.  jpeg.hip runs it in lane 0 of a one-wave workgroup
 // (jpeg_entropy_kernel); jpeg_host.cpp runs the same code on the CPU (hoig_jpeg_entropy_host), which is what the CPU suite pins.
 //
+// (jpeg_parallel.h builds the decode that is parallel inside an interval on the tables, the symbol decode and the geometry of this file.)
+//
 // What differs between the two is only WHERE bytes come from and where a finished block goes, and that is the `Ctx` parameter:
 //   uint8_t  byte(int pos)        one byte of the scan data (pos < the interval's end: the reader never asks beyond it)
 //   void     window(int pos)      called by EVERYONE between blocks: make [pos, pos + JPEG_BLOCK_MAX_BYTES) readable (device: the LDS window)
@@ -111,9 +113,9 @@ struct JpegBits {
     JPEG_HD int unread() const { return (end - pos) + (n - fake * 8) / 8; }
 };
 
-// one Huffman symbol; -1: no code of 16 bits or fewer matches
-template <class Ctx>
-JPEG_HD inline int jpeg_symbol(JpegBits<Ctx> &br, const JpegHuff *h) {
+// one Huffman symbol; -1: no code of 16 bits or fewer matches  (Bits: JpegBits, or jpeg_parallel.h's reader)
+template <class Bits>
+JPEG_HD inline int jpeg_symbol(Bits &br, const JpegHuff *h) {
     const unsigned e = h->look[br.peek(8)];
     if (e) {
         br.drop((int)(e >> 8));

@@ -22,7 +22,7 @@ _JPEG_KEYS = ('frame', 'jpeg', 'jpeg_plan')
 
 def _collate_jpeg(recs):
     """The frame part of a view whose records carry JPEG files (opt.device_jpeg): 'jpeg' = the files packed into ONE byte buffer with
-    their plan records and interval offsets (jpeg.pack: what hoig_jpeg_decode_bgr_u8 takes; one pinned buffer, one H2D copy), the
+    their plan records and interval offsets (jpeg.pack: what the decode entry points take; one pinned buffer, one H2D copy), the
     batch slot, path and size of each; 'frame' = per sample the decoded frame of a record that has one (a PNG, a progressive file),
     else None.  Image i decodes into slot i of the batch's [B][Hs][Ws][3] buffer."""
     from . import jpeg as J
@@ -71,6 +71,10 @@ class MeshCache(object):
 
 
 class DeviceStage(object):
+    # the entry point that decodes a batch's JPEG files: the one that is parallel inside a restart interval, or (for a comparison:
+    # tools/bench_jpeg.py) 'hoig_jpeg_decode_bgr_u8', which is serial there
+    JPEG_ENTRY = 'hoig_jpeg_decode_bgr_u8_par'
+
     def __init__(self, dataset, device=None, prepare=None):
         """prepare (optional): batch dict -> dict of further entries, run on the loader stream right behind the batch's pixel work --
         i.e. ONE BATCH AHEAD of the step that consumes it.  ``CustomDatasetDataLoader`` passes the raw-batch stage of
@@ -84,24 +88,27 @@ class DeviceStage(object):
         self._meshes = MeshCache(dataset, self.device)
         self._max_verts = dataset.max_obj_verts
         self._stream = None
-        self._decodes = []                              # (event, pinned status words, paths) of the JPEG decodes of the batch being issued
+        self._decodes = []                              # (event, pinned status words, paths, pinned plans) of the JPEG decode of the batch being issued
 
     # ---- one view (A or B) of a batch
-    def _images(self, col):
-        L, dev = self._L, self.device
+    @staticmethod
+    def _frame_size(col):
+        """(Hs, Ws) of a view whose records carry JPEG files; the frames (and the masks) of a view must have one size"""
         frames, masks, files = col['frame'], col.get('mask'), col.get('jpeg')
         sizes = set(tuple(hw) for hw in files['sizes']) | set(tuple(f.shape[:2]) for f in frames if f is not None) if files else ()
         if not (torch.is_tensor(frames) or len(sizes) == 1) or not (masks is None or torch.is_tensor(masks)):
             raise ValueError('the frames (and the masks) of a batch must have one size')
+        return next(iter(sizes)) if files else None
+
+    def _images(self, col, f_dev=None):
+        """f_dev: the view's [B][Hs][Ws][3] frames where _decode_jpeg made them (opt.device_jpeg: the workers sent files, not pixels)"""
+        L, dev = self._L, self.device
+        frames, masks = col['frame'], col.get('mask')
+        self._frame_size(col)
         st = torch.cuda.current_stream().cuda_stream
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        if files:                                       # opt.device_jpeg: the workers sent files, not pixels
-            (Hs, Ws), B = next(iter(sizes)), len(frames)
-            f_dev = torch.empty((B, Hs, Ws, 3), dtype=torch.uint8, device=dev)
-            for i, f in enumerate(frames):              # (the records the host decoded: not a JPEG, or not one the device takes)
-                if f is not None:
-                    f_dev[i].copy_(f, non_blocking=True)
-            self._decode_jpeg(files, f_dev)
+        if f_dev is not None:
+            B, Hs, Ws, _ = f_dev.shape
         else:
             B, Hs, Ws, _ = frames.shape
             f_dev = frames.to(dev, non_blocking=True)
@@ -118,27 +125,65 @@ class DeviceStage(object):
         L.call('hoig_warp_affine_u8', p(big), B, MASK_SIZE[1], MASK_SIZE[0], 3, p(m_dev), PATCH, PATCH, 2, p(mask), st)
         return image, mask, torch.from_numpy(trans)
 
-    def _decode_jpeg(self, files, out):
-        """hoig_jpeg_decode_bgr_u8 on the packed files of a view, into their slots of ``out``; the status words go back through pinned
-        memory behind an event of their own, for ``finish`` to read."""
+    def _decode_jpeg(self, cols):
+        """The JPEG files of ALL views of a batch in ONE call of JPEG_ENTRY: the views' packed files go into one device buffer one behind
+        the other, their plan records into one array (a later view's offsets moved behind the earlier views' bytes, interval offsets
+        and frames), and the result straight into the views' [B][Hs][Ws][3] frame buffers, which are slices of one allocation.  The
+        status words go back through pinned memory behind an event of their own, for ``finish`` to read.  -> per view its frame
+        buffer, or None for a view whose records carry pixels."""
+        from . import jpeg as J
         L, dev = self._L, self.device
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        plans = files['plans']
-        n = len(files['slots'])
-        work_bytes = L.lib.hoig_jpeg_decode_workspace_bytes(p(plans), n)        # (writes the workspace offsets into the host records)
+        views = [(k, col, self._frame_size(col)) for k, col in enumerate(cols) if col.get('jpeg')]
+        if not views:
+            return [None] * len(cols)
+        shapes = [(len(col['frame']), hw[0], hw[1], 3) for _, col, hw in views]
+        out_at = np.concatenate([[0], np.cumsum([-(-int(np.prod(sh)) // 256) * 256 for sh in shapes])])     # (each view 256-byte aligned)
+        out = torch.empty(int(out_at[-1]), dtype=torch.uint8, device=dev)
+        result = [None] * len(cols)
+        recs, byte_at, entry_at, paths = [], 0, 0, []
+        for v, (k, col, _) in enumerate(views):
+            files = col['jpeg']
+            f_dev = out[int(out_at[v]):int(out_at[v]) + int(np.prod(shapes[v]))].view(shapes[v])
+            for i, f in enumerate(col['frame']):        # (the records the host decoded: not a JPEG, or not one the device takes)
+                if f is not None:
+                    f_dev[i].copy_(f, non_blocking=True)
+            r = files['plans'].numpy().view(J.PLAN_DTYPE).copy()
+            r['data_off'] += byte_at
+            r['interval_first'] += entry_at
+            r['out_off'] += int(out_at[v])
+            recs.append(r)
+            byte_at += files['bytes'].numel()
+            entry_at += files['intervals'].numel()
+            paths += files['paths']
+            result[k] = f_dev
+        n = sum(len(r) for r in recs)
+        plans = torch.empty(n * J.PLAN_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        plans.numpy().view(J.PLAN_DTYPE)[:] = np.concatenate(recs)
+        par = self.JPEG_ENTRY.endswith('_par')
+        work_bytes = (L.lib.hoig_jpeg_decode_par_workspace_bytes(p(plans), n, 0) if par else
+                      L.lib.hoig_jpeg_decode_workspace_bytes(p(plans), n))     # (writes the workspace offsets into the host records)
         if work_bytes < 0:
-            raise ValueError('a JPEG plan outside the supported set: %s' % files['paths'])
-        data, plans_dev = files['bytes'].to(dev, non_blocking=True), plans.to(dev, non_blocking=True)
-        intervals = files['intervals'].to(dev, non_blocking=True)
+            raise ValueError('a JPEG plan outside the supported set: %s' % paths)
+        data = torch.empty(byte_at, dtype=torch.uint8, device=dev)
+        intervals = torch.empty(entry_at, dtype=torch.int32, device=dev)
+        byte_at = entry_at = 0
+        for _, col, _ in views:
+            b, iv = col['jpeg']['bytes'], col['jpeg']['intervals']
+            data[byte_at:byte_at + b.numel()].copy_(b, non_blocking=True)
+            intervals[entry_at:entry_at + iv.numel()].copy_(iv, non_blocking=True)
+            byte_at, entry_at = byte_at + b.numel(), entry_at + iv.numel()
+        plans_dev = plans.to(dev, non_blocking=True)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        L.call('hoig_jpeg_decode_bgr_u8', p(data), data.numel(), p(plans), p(plans_dev), n, p(intervals), intervals.numel(), p(out),
-               out.numel(), p(status), p(work), work_bytes, torch.cuda.current_stream().cuda_stream)
+        L.call(self.JPEG_ENTRY, p(data), data.numel(), p(plans), p(plans_dev), n, p(intervals), intervals.numel(), p(out), out.numel(),
+               p(status), p(work), work_bytes, *(((0,) if par else ()) + (torch.cuda.current_stream().cuda_stream,)))
         back = torch.empty(n, dtype=torch.int32, pin_memory=True)
         back.copy_(status, non_blocking=True)
         decoded = torch.cuda.Event()
         decoded.record()
-        self._decodes.append((decoded, back, files['paths']))
+        self._decodes.append((decoded, back, paths, plans))         # (plans: the pinned source of a copy that may not have run yet)
+        return result
 
     def _object_vertices(self, col):
         """hov3_dataset.py:246-248: zeros((7866, 3), float32); [:n] = v @ Rodrigues(objRot).T + objTrans; ycb_dataset.py:165-169,292-293:
@@ -163,8 +208,8 @@ class DeviceStage(object):
             out[idx, :v.shape[0]] = now.float()
         return out
 
-    def _view(self, col):
-        image, mask, trans = self._images(col)
+    def _view(self, col, f_dev=None):
+        image, mask, trans = self._images(col, f_dev)
         dev = self.device
         mano = {'cam': col['cam'].to(dev, non_blocking=True), 'trans': trans.to(dev, non_blocking=True),
                 'pose': col['pose'].to(dev, non_blocking=True), 'shape': col['shape'].to(dev, non_blocking=True)}
@@ -181,7 +226,8 @@ class DeviceStage(object):
             self._stream = ops.new_stream(self.device, 'loader')
         self._decodes = []
         with torch.cuda.stream(self._stream):
-            a, b = self._view(raw['A']), self._view(raw['B'])
+            frames = self._decode_jpeg([raw['A'], raw['B']])        # opt.device_jpeg: both views' files, one call
+            a, b = self._view(raw['A'], frames[0]), self._view(raw['B'], frames[1])
             batch = {'imageA': a[0], 'maskA': a[1], 'manoA': a[2], 'nameA': a[3],
                      'imageB': b[0], 'maskB': b[1], 'manoB': b[2], 'nameB': b[3]}
             if a[1] is None:                                                # ycb_dataset.py:278-279: no mask keys
@@ -194,7 +240,7 @@ class DeviceStage(object):
 
     def finish(self, pending):
         batch, done, (_, decodes) = pending
-        for decoded, status, paths in decodes:          # opt.device_jpeg: a file the device could not decode is an error HERE
+        for decoded, status, paths, _ in decodes:          # opt.device_jpeg: a file the device could not decode is an error HERE
             decoded.synchronize()
             bad = ['%s (%s)' % (path, self._jpeg_status(word)) for path, word in zip(paths, status.tolist()) if word]
             if bad:

@@ -6,7 +6,7 @@ tables, DRI, where the scan's entropy-coded data lies and where its restart inte
 supported set -- the caller then decodes that file on the host as before.  Supported: baseline and extended-sequential Huffman (SOF0 /
 SOF1), 8-bit, one interleaved scan, YCbCr 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2) or a single component, EXIF orientation 1 or none.
 
-``pack(items)`` lays a batch's files and plans out for ``hoig_jpeg_decode_bgr_u8``: one byte buffer, the plan records
+``pack(items)`` lays a batch's files and plans out for ``hoig_jpeg_decode_bgr_u8`` / ``hoig_jpeg_decode_bgr_u8_par``: one byte buffer, the plan records
 (``PLAN_DTYPE`` restates ``hoig_jpeg_plan`` of include/hoig_kernels.h) and the interval offsets."""
 import struct
 

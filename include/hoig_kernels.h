@@ -688,6 +688,27 @@ int hoig_jpeg_decode_bgr_u8(const uint8_t *bytes, int64_t nbytes, const hoig_jpe
 int hoig_jpeg_reconstruct_bgr_u8(const hoig_jpeg_plan *plans_host, const hoig_jpeg_plan *plans_dev, int n, uint8_t *out,
                                  int64_t out_bytes, void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
 
+/* ---- The same decode with the entropy stage PARALLEL INSIDE a restart interval (hoig_amd/csrc/jpeg_parallel.h: self-synchronising
+ *      sub-sequences of `subseq_bytes` raw bytes, one lane each), for files without restart markers.  Five launches per batch: the
+ *      coefficients are zeroed, a workgroup per image and interval decodes, the serial kernel above decodes again the intervals that
+ *      workgroup found irregular (a corrupt stream: so status[i] is what hoig_jpeg_decode_bgr_u8 writes), then the two reconstruction
+ *      kernels.  subseq_bytes: 0 (HOIG_JPEG_SUBSEQ_BYTES), 32, 64, 128 or 256; anything else is HOIG_EINVAL. ---- */
+#define HOIG_JPEG_SUBSEQ_BYTES 64
+/* HOST: hoig_jpeg_decode_workspace_bytes (the same coef_off / plane_off), plus the parallel decoder's table behind the planes */
+int64_t hoig_jpeg_decode_par_workspace_bytes(hoig_jpeg_plan *plans, int n, int subseq_bytes);
+/* HOST twin of the parallel entropy kernel: the same code, a workgroup of `lanes` lanes walked round by round (no HIP call).  Arguments
+ * as hoig_jpeg_entropy_host; the coefficient part of each image is zeroed first.  rounds (optional) [n]: the largest number of decode
+ * rounds among image i's intervals.  states (optional) [n_states][4]: per sub-sequence, image after image and interval after interval,
+ * the final (bit offset, block in MCU, zigzag position, completed blocks); zeros for an interval that went to the serial code. */
+int hoig_jpeg_entropy_par_host(const uint8_t *bytes, int64_t nbytes, const hoig_jpeg_plan *plans, int n, const int32_t *intervals,
+                               int64_t n_entries, int subseq_bytes, int lanes, void *coef, int64_t coef_bytes, int32_t *status,
+                               int32_t *rounds, int32_t *states, int64_t n_states);
+/* hoig_jpeg_decode_bgr_u8 with the parallel entropy stage; workspace: hoig_jpeg_decode_par_workspace_bytes.  Same promises: status[i]
+ * as the serial entry writes it, never synchronises, allocates nothing, the plans are checked on the host. */
+int hoig_jpeg_decode_bgr_u8_par(const uint8_t *bytes, int64_t nbytes, const hoig_jpeg_plan *plans_host, const hoig_jpeg_plan *plans_dev,
+                                int n, const int32_t *intervals, int64_t n_entries, uint8_t *out, int64_t out_bytes, int32_t *status,
+                                void *workspace, int64_t workspace_bytes, int subseq_bytes, hoig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

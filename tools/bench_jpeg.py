@@ -3,9 +3,12 @@
 Batches of 16 frames (batch 8, two views), 640 x 480, 4:2:0, quality 90, of the test fixture's smooth-plus-noise content -- synthetic: no
 real HO3D-v3 or DexYCB frame has been measured -- without restart markers and with one restart interval per MCU row.
   host    seconds per frame in this process: Pillow decode (imread_bgr), and file read + jpeg.parse (what a worker does with the option)
-  device  one batch's decode alone, by events (20 repetitions after a warm-up), and its H2D bytes against 16 x 921,600
+  device  one batch's decode alone, by events (20 repetitions after a warm-up), through the serial entry point (hoig_jpeg_decode_bgr_u8)
+          and through the one that is parallel inside a restart interval (hoig_jpeg_decode_bgr_u8_par) at every sub-sequence size, with
+          the decode rounds per frame that the host twin counts for the same workgroup; and its H2D bytes against 16 x 921,600
   step    the loader-fed training step (tools/bench_loader_step.py's last leg: workers + DeviceStage + raw stage one batch ahead +
-          set_input + step) on a tree of JPEG frames, option off and on alternating, `rounds` rounds
+          set_input + step) on a tree of JPEG frames: option off, on with the serial entry point, on with the parallel one (one call
+          per batch either way), alternating, `rounds` rounds
 usage: python tools/bench_jpeg.py [--out FILE] [--steps 24] [--workers 4] [--rounds 3] [--decode-only]
 (--decode-only: just the device leg, for a `rocprofv3 --kernel-trace --stats -- python tools/bench_jpeg.py --decode-only` run)"""
 import argparse
@@ -48,12 +51,27 @@ def encode(img, restart):
     return buf.getvalue()
 
 
-def device_leg(datas, label, reps=20):
-    """-> ms per batch (median of reps), the decode call alone: the files are already on the device"""
+def host_rounds(buf, recs, ivs, n, subseq):
+    """decode rounds per frame, from the host twin walking the device's workgroup (512 / 256 / 128 lanes for 32, 64 / 128 / 256 bytes)"""
+    q = lambda a: ctypes.c_void_p(a.ctypes.data)
+    work = np.zeros(int(recs[0]['plane_off']), np.uint8)
+    status, rounds = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    L.call('hoig_jpeg_entropy_par_host', q(buf), buf.size, q(recs), n, q(ivs), ivs.size, subseq, min(512, 32768 // subseq), q(work),
+           work.size, q(status), q(rounds), None, 0)
+    assert not status.any()
+    return rounds
+
+
+def device_leg(datas, label, reps=20, subseq=None):
+    """-> (ms per batch: median of reps, spread), the decode call alone: the files are already on the device.  subseq None: the serial
+    entry point; else the parallel one with sub-sequences of that many bytes"""
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     plans = [J.parse(d) for d in datas]
     buf, recs, ivs = J.pack(list(zip(datas, plans)))
-    size = L.lib.hoig_jpeg_decode_workspace_bytes(ctypes.c_void_p(recs.ctypes.data), len(datas))
+    if subseq is None:
+        size = L.lib.hoig_jpeg_decode_workspace_bytes(ctypes.c_void_p(recs.ctypes.data), len(datas))
+    else:
+        size = L.lib.hoig_jpeg_decode_par_workspace_bytes(ctypes.c_void_p(recs.ctypes.data), len(datas), subseq)
     total = sum(q['width'] * q['height'] * 3 for q in plans)
     out = torch.empty(total, dtype=torch.uint8, device='cuda')
     work = torch.empty(size, dtype=torch.uint8, device='cuda')
@@ -62,8 +80,9 @@ def device_leg(datas, label, reps=20):
     st = torch.cuda.current_stream().cuda_stream
 
     def run():
-        L.call('hoig_jpeg_decode_bgr_u8', p(b_dev), b_dev.numel(), ctypes.c_void_p(recs.ctypes.data), p(r_dev), len(datas), p(i_dev),
-               i_dev.numel(), p(out), total, p(status), p(work), size, st)
+        L.call('hoig_jpeg_decode_bgr_u8' if subseq is None else 'hoig_jpeg_decode_bgr_u8_par', p(b_dev), b_dev.numel(),
+               ctypes.c_void_p(recs.ctypes.data), p(r_dev), len(datas), p(i_dev), i_dev.numel(), p(out), total, p(status), p(work), size,
+               *(((subseq,) if subseq is not None else ()) + (st,)))
     for _ in range(3):
         run()
     torch.cuda.synchronize()
@@ -79,11 +98,17 @@ def device_leg(datas, label, reps=20):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     h2d = buf.size + recs.nbytes + ivs.nbytes
-    say('%-22s: decode of one batch alone %.3f ms (median of %d; min %.3f, max %.3f); %d restart intervals per frame; equal to Pillow, every byte'
-        % (label, float(np.median(ms)), reps, min(ms), max(ms), len(plans[0]['intervals']) - 1))
-    say('%-22s  H2D per batch %d bytes (files %d + plans %d + interval offsets %d) against %d of decoded frames: %.1f%%'
-        % ('', h2d, buf.size, recs.nbytes, ivs.nbytes, len(datas) * 921600, 100.0 * h2d / (len(datas) * 921600)))
-    return float(np.median(ms))
+    how = 'serial entry' if subseq is None else 'parallel, %3d bytes' % subseq
+    say('%-22s %-19s: decode of one batch alone %.3f ms (median of %d; min %.3f, max %.3f); %d restart intervals per frame; equal to Pillow, every byte'
+        % (label, how, float(np.median(ms)), reps, min(ms), max(ms), len(plans[0]['intervals']) - 1))
+    if subseq is None:
+        say('%-22s  H2D per batch %d bytes (files %d + plans %d + interval offsets %d) against %d of decoded frames: %.1f%%'
+            % ('', h2d, buf.size, recs.nbytes, ivs.nbytes, len(datas) * 921600, 100.0 * h2d / (len(datas) * 921600)))
+    else:
+        r = host_rounds(buf, recs, ivs, len(datas), subseq)
+        say('%-22s  decode rounds per frame (the largest among its intervals): median %d, min %d, max %d; sub-sequences per frame: median %d'
+            % ('', int(np.median(r)), r.min(), r.max(), int(np.median([-(-q['scan_length'] // subseq) for q in plans]))))
+    return float(np.median(ms)), max(ms) - min(ms)
 
 
 frames = [R.content(640, 480, k) for k in range(16)]
@@ -91,8 +116,19 @@ plain, restart = [encode(f, False) for f in frames], [encode(f, True) for f in f
 say('frames: 16 x 640 x 480, 4:2:0, quality 90, synthetic smooth-plus-noise content (tests/data_fixture.py); NO real HO3D-v3 / DexYCB frame was measured')
 say('bytes per frame: %.0f without restart markers, %.0f with one interval per MCU row (decoded: 921600)'
     % (np.mean([len(d) for d in plain]), np.mean([len(d) for d in restart])))
-ms_plain = device_leg(plain, 'no restart markers')
-ms_restart = device_leg(restart, 'one interval per row')
+SUBSEQ = (32, 64, 128, 256)
+ms_plain, sp_plain = device_leg(plain, 'no restart markers')
+par_plain = {S: device_leg(plain, 'no restart markers', subseq=S) for S in SUBSEQ}
+ms_restart, sp_restart = device_leg(restart, 'one interval per row')
+par_restart = {S: device_leg(restart, 'one interval per row', subseq=S) for S in SUBSEQ}
+S0 = L.JPEG_SUBSEQ_BYTES
+say('conditions, at the default of %d bytes (HOIG_JPEG_SUBSEQ_BYTES):' % S0)
+say('  no restart markers  : parallel %.3f ms < serial %.3f ms by more than the two spreads (%.3f + %.3f): %s'
+    % (par_plain[S0][0], ms_plain, par_plain[S0][1], sp_plain,
+       'MET' if ms_plain - par_plain[S0][0] > par_plain[S0][1] + sp_plain else 'NOT MET'))
+say('  one interval per row: parallel %.3f ms not above serial %.3f ms by more than the two spreads (%.3f + %.3f): %s'
+    % (par_restart[S0][0], ms_restart, par_restart[S0][1], sp_restart,
+       'MET' if par_restart[S0][0] - ms_restart <= par_restart[S0][1] + sp_restart else 'NOT MET'))
 if args.decode_only:
     sys.exit(0)
 
@@ -123,7 +159,7 @@ from test_hand_recovery_gpu import _assets                 # noqa: E402
 from test_jpeg_cpu import jpeg_frames                      # noqa: E402
 from common import opt_namespace                           # noqa: E402
 from hoig_amd import ops                                   # noqa: E402
-from hoig_amd.data import CustomDatasetDataLoader          # noqa: E402
+from hoig_amd.data import CustomDatasetDataLoader, DeviceStage   # noqa: E402
 from hoig_amd.mano import ManoModel                        # noqa: E402
 from hoig_amd.models import ModelsFactory                  # noqa: E402
 from oracle import mano_oracle as M                        # noqa: E402
@@ -144,8 +180,9 @@ with tempfile.TemporaryDirectory() as root:
     model = ModelsFactory.get_by_name('trainer', opt, use_ddp=False)
     model.set_train()
 
-    def leg(on):
+    def leg(on, entry='hoig_jpeg_decode_bgr_u8_par'):
         opt_d.device_jpeg = on
+        DeviceStage.JPEG_ENTRY = entry
         k, t = 0, None
         for b in CustomDatasetDataLoader(opt_d, is_for_train=True).load_data():
             if k == 4:                                      # (the first batches pay the worker start-up)
@@ -157,18 +194,22 @@ with tempfile.TemporaryDirectory() as root:
         torch.cuda.synchronize()
         return (time.perf_counter() - t) / (k - 4) * 1e3
     leg(False)                                              # warm-up of everything the timed legs use
+    leg(True, 'hoig_jpeg_decode_bgr_u8')
     leg(True)
-    off, on = [], []
+    off, ser, on = [], [], []
     for _ in range(args.rounds):
         off.append(leg(False))
+        ser.append(leg(True, 'hoig_jpeg_decode_bgr_u8'))
         on.append(leg(True))
 say('loader-fed step (batch 8 = 16 frames per step, %d workers, %d timed steps per leg, %d rounds alternating):' % (args.workers, steps, args.rounds))
 say('  option off: %s ms   (mean %.2f, spread %.2f)' % (' / '.join('%.2f' % v for v in off), np.mean(off), max(off) - min(off)))
-say('  option on : %s ms   (mean %.2f, spread %.2f)' % (' / '.join('%.2f' % v for v in on), np.mean(on), max(on) - min(on)))
-step = float(np.mean(off))
-say('condition (a batch\'s decode alone must take less than the step, or the loader cannot stay one batch ahead): %.3f ms < %.2f ms: %s'
-    % (ms_plain, step, 'MET' if ms_plain < step else 'NOT MET -- the option does not pay yet'))
-say('  (frames written with one restart interval per MCU row: %.3f ms)' % ms_restart)
+say('  option on, serial entry, one call per batch  : %s ms   (mean %.2f, spread %.2f)'
+    % (' / '.join('%.2f' % v for v in ser), np.mean(ser), max(ser) - min(ser)))
+say('  option on, parallel entry, one call per batch: %s ms   (mean %.2f, spread %.2f)'
+    % (' / '.join('%.2f' % v for v in on), np.mean(on), max(on) - min(on)))
+gap = float(np.mean(on) - np.mean(off))
+say('the step with the option on (parallel) against off: %+.2f ms (%s)'
+    % (gap, 'within the spreads' if abs(gap) <= (max(on) - min(on)) + (max(off) - min(off)) else ('SLOWER' if gap > 0 else 'faster')))
 if args.out:
     with open(args.out, 'w') as f:
         f.write('\n'.join(lines) + '\n')
