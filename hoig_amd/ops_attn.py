@@ -17,8 +17,10 @@ def attn_index_clear():
 
 def _attn_pixel_index(flow, B, H, W):
     """The bucket index of a flow field (hoig_attn_build_index), built once per flow tensor: every attention layer of a
-    resolution shares its flow (generator.py:480-491), and the backward of each needs the same index."""
-    key = (flow.data_ptr(), B, H, W, torch.cuda.current_stream().cuda_stream)
+    resolution shares its flow (generator.py:480-491), and the backward of each needs the same index.  The key carries the tensor's
+    version counter: a buffer that is rewritten in place between two steps (flow.copy_(...)) keeps its address, and the index of the
+    field it held before would gather the wrong pixels."""
+    key = (flow.data_ptr(), flow._version, B, H, W, torch.cuda.current_stream().cuda_stream)
     hit = _attn_index.get(key)
     if hit is None:
         idx = torch.empty(L.lib.hoig_attn_index_ints(B, H, W), dtype=torch.int32, device=flow.device)

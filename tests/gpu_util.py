@@ -21,3 +21,11 @@ def rel_err(a, b):
 def rel_l2(a, b):
     a, b = a.detach().float().cpu(), b.detach().float().cpu()
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+
+
+def poison_free_memory():
+    """Leave NaNs in the caching allocator's free blocks of both pools, so that an output a kernel fails to write (the operators hand
+    out torch.empty tensors) reads as NaN and not as whatever an earlier, correct run left at the same address."""
+    nan = float('nan')
+    blocks = [torch.full((16 << 20,), nan, device='cuda')] + [torch.full((1 << 18,), nan, device='cuda') for _ in range(32)]
+    del blocks
