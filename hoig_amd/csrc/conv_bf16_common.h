@@ -221,6 +221,8 @@ struct FlatArgs {
     int nblk, nblk_n, steps_per_split;
 };
 int launch_flat_m16(FlatArgs a, int ns, hipStream_t st);
+// conv_halo5.hip: valid 5x5 convolutions (and their data gradients) over maps too wide for the flattened axis, on 16 x 16 pixel tiles
+int launch_halo5_m16(FlatArgs a, int ns, hipStream_t st);
 
 // argument block of the weight-gradient halo kernels (wgrad_halo_bf16_kernel in conv_igemm_bf16.hip, wgrad_dma.hip)
 struct WHaloArgs {

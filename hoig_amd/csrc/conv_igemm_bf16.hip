@@ -1540,6 +1540,11 @@ int run(const Conv &q) {
         }
         const int rc = launch_flat_m16(f, ns, st);
         if (rc != HOIG_EUNSUPPORTED) return rc;
+        // the wide maps (72 / 68 / 136 / 132 pixels), whose flattened halo does not fit: 16 x 16 pixel tiles (conv_halo5.hip)
+        if (hoig_tuning(HOIG_TUNE_HALO5) != 0) {
+            const int rc5 = launch_halo5_m16(f, ns, st);
+            if (rc5 != HOIG_EUNSUPPORTED) return rc5;
+        }
     }
     // stride-2 3x3 pad-1 layers on the parity-phase halo kernel.  gather: Conv2d forward / ConvTranspose2d data gradient;
     // scatter: ConvTranspose2d forward / Conv2d data gradient

@@ -21,6 +21,10 @@ Entry g_table[HOIG_TUNE_COUNT] = {
     {"s2_pipe", 1},
     {"norm_in", 1},
     {"wino8", 0},
+    // the attention's WIDE valid 5x5 layers (72 / 68 / 136 / 132 pixels, which the flattened-axis kernel declines) on the 2-D-tiled
+    // halo kernel of conv_halo5.hip, forward and data gradient; 0: the generic implicit GEMM, as before that kernel existed;
+    // 2: as 1, without its split over K on launches of few tiles
+    {"halo5", 1},
 };
 }  // namespace
 
