@@ -138,6 +138,7 @@ _SIGS = {
     'hoig_stream_destroy': [_vp],
     'hoig_stream_scratch_set': [_vp, _vp, _i64],
     'hoig_tensor2im_u8': [_vp, _vp] + [_i] * 6 + [_vp],
+    'hoig_tensor2im_nhwc_u8': [_vp, _vp, _i64, _i, _vp],
     'hoig_prep_texture': [_vp] * 9,
     'hoig_prep_lookup': [_vp] * 5 + [_i] + [_vp] * 8,
     'hoig_prep_assemble': [_i] + [_vp] * 17 + [_i] + [_vp] * 6,
@@ -159,6 +160,10 @@ _SIGS = {
     'hoig_jpeg_reconstruct_bgr_u8': [_vp, _vp, _i, _vp, _i64, _vp, _i64, _vp],
     'hoig_jpeg_entropy_par_host': [_vp, _i64, _vp, _i, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _i64],
     'hoig_jpeg_decode_bgr_u8_par': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp],
+    'hoig_pil_bilinear_ksize': [_i, _i],
+    'hoig_pil_bilinear_table': [_i, _i, _vp],
+    'hoig_resize_pil_bilinear_u8_host': [_vp, _i, _i, _i, _i, _vp, _i, _i],
+    'hoig_resize_pil_bilinear_u8': [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
 }
 
 
@@ -194,6 +199,8 @@ def _load():
     lib.hoig_lpips_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_ssim_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
     lib.hoig_ssim_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_resize_pil_bilinear_u8_workspace_bytes.argtypes = [_i] * 6
+    lib.hoig_resize_pil_bilinear_u8_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]

@@ -529,6 +529,14 @@ __global__ __launch_bounds__(NT) void adam_dev_kernel(float *__restrict__ p, con
     }
 }
 
+// utils/util.py:249-264: (x + 1) / 2 * 255, then numpy's astype(uint8) of a float: C-style truncation, wrap on out-of-range (values
+// here are in range)
+__device__ __forceinline__ uint8_t tensor2im_byte(float v, int unnorm) {
+    if (unnorm) { v += 1.0f; v /= 2.0f; }
+    v *= 255.0f;
+    return (uint8_t)((int)v & 0xFF);
+}
+
 __global__ void tensor2im_kernel(const float *__restrict__ x, uint8_t *__restrict__ out, int B, int H, int W, int C,
                                  int ncol, int nrw, int unnorm) {
     // out: [C][nrw*H][ncol*W] uint8 ; x NHWC
@@ -539,14 +547,14 @@ __global__ void tensor2im_kernel(const float *__restrict__ x, uint8_t *__restric
         const int w = (int)(p % W);
         p /= W;
         const int h = (int)(p % H), b = (int)(p / H);
-        float v = x[i];
-        if (unnorm) { v += 1.0f; v /= 2.0f; }
-        v *= 255.0f;
         const int gr = b / ncol, gc = b % ncol;
-        // numpy astype(uint8) of a float: C-style truncation, wrap on out-of-range (values here are in range)
-        const int iv = (int)v;
-        out[((size_t)c * (nrw * H) + gr * H + h) * ((size_t)ncol * W) + gc * W + w] = (uint8_t)(iv & 0xFF);
+        out[((size_t)c * (nrw * H) + gr * H + h) * ((size_t)ncol * W) + gc * W + w] = tensor2im_byte(x[i], unnorm);
     }
+}
+
+// the same bytes sample by sample, in the layout of x: uint8 [B][H][W][C] (what eval.py crops out of the grid again)
+__global__ void tensor2im_nhwc_kernel(const float *__restrict__ x, uint8_t *__restrict__ out, int64_t n, int unnorm) {
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) out[i] = tensor2im_byte(x[i], unnorm);
 }
 
 }  // namespace
@@ -764,6 +772,13 @@ extern "C" int hoig_tensor2im_u8(const float *x, uint8_t *out, int B, int H, int
     const int nrw = (B + ncol - 1) / ncol;
     tensor2im_kernel<<<hoig_stream_grid((int64_t)B * H * W * C, NT), NT, 0, ST>>>(x, out, B, H, W, C, ncol, nrw,
                                                                                  unnormalize);
+    HOIG_LAUNCH_CHECK();
+    return HOIG_OK;
+}
+extern "C" int hoig_tensor2im_nhwc_u8(const float *x, uint8_t *out, int64_t n, int unnormalize, hoig_stream_t stream) {
+    if (!x || !out || n < 0) return HOIG_EINVAL;
+    if (n == 0) return HOIG_OK;
+    tensor2im_nhwc_kernel<<<hoig_stream_grid(n, NT), NT, 0, ST>>>(x, out, n, unnormalize);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

@@ -9,7 +9,8 @@ The reference's evaluation loop (HOIG_HOv3/eval.py:59-79) turns ``get_current_vi
 where the three visuals are uint8 CHW batch grids (utils/util.py:249-264, ``make_grid(nrow=int(sqrt(B)), padding=0)``)
 and crop (r, c) = (i // cols, i % cols) with cols = grid_width // side.  The grids come from the fused
 denormalise + tile kernel (``hoig_tensor2im_u8``), one device-to-host copy per grid; encoding and file writes run on a small
-thread pool so that the next batch's forward is not held up by zlib (the reference writes synchronously).
+thread pool so that the next batch's forward is not held up by zlib (the reference writes synchronously).  ``write_images`` writes the
+same files from the per-sample device bytes of ``Trainer.eval_images_u8`` (no visuals, no grid).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -59,12 +60,27 @@ class EvalWriter(object):
             raise ValueError('nameA / nameB length mismatch')
         for sub, key in self.grids:
             for crop, a, b in zip(crops_of(visuals[key], len(names_a), self.side), names_a, names_b):
-                path = os.path.join(self.out_dir, sub, pair_name(a, b))
-                if self._pool is None:
-                    _save_png(crop, path)
-                else:
-                    self._pending.append(self._pool.submit(_save_png, crop.copy(), path))
-                self.written += 1
+                self._save(crop, os.path.join(self.out_dir, sub, pair_name(a, b)))
+
+    def write_images(self, images_u8, names_a, names_b):
+        """The files of write() from Trainer.eval_images_u8's dict (uint8 [B,H,W,3] per set, on the device or the host): one
+        device-to-host copy per set, no grid to crop.  Scoring in memory (hoig_amd.metrics.stream) and keeping the PNGs share a loop."""
+        if len(names_a) != len(names_b):
+            raise ValueError('nameA / nameB length mismatch')
+        for sub, _ in self.grids:
+            batch = images_u8[sub]
+            batch = batch.cpu().numpy() if hasattr(batch, 'cpu') else np.asarray(batch)
+            if batch.ndim != 4 or batch.dtype != np.uint8 or batch.shape[0] < len(names_a):
+                raise ValueError('%s: uint8 [B,H,W,C] with B >= %d expected, got %s %s' % (sub, len(names_a), batch.dtype, batch.shape))
+            for crop, a, b in zip(batch, names_a, names_b):
+                self._save(crop, os.path.join(self.out_dir, sub, pair_name(a, b)), owned=True)
+
+    def _save(self, crop, path, owned=False):
+        if self._pool is None:
+            _save_png(crop, path)
+        else:
+            self._pending.append(self._pool.submit(_save_png, crop if owned else crop.copy(), path))
+        self.written += 1
 
     def close(self):
         for f in self._pending:

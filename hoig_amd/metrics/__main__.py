@@ -18,6 +18,8 @@ def parser():
     p.add_argument('--alexnet-weights', default=None, help='alexnet-owt-7be5be79.pth')
     p.add_argument('--lpips-weights', default=None, help='lpips_weights.ckpt')
     p.add_argument('--precision', default=None, help="convolution arithmetic: 'bf16x3' (default) or 'f32'")
+    p.add_argument('--device-resize', action='store_true',
+                   help='lpips / ssim: run the two PIL resizes of get_eval_loader on the device (the same bytes; workers only decode)')
     return p
 
 
@@ -35,11 +37,11 @@ def main(argv=None):
     elif a.metric == 'lpips':
         from .lpips import calculate_lpips_given_paths
         v = calculate_lpips_given_paths(a.path, a.img_size, a.batch_size or 50, a.alexnet_weights, a.lpips_weights, a.precision,
-                                        a.device)
+                                        a.device, device_resize=a.device_resize)
         print('LPIPS: ', v)
     else:
         from .ssim import calculate_ssim_given_paths
-        v = calculate_ssim_given_paths(a.path, a.img_size, a.batch_size or 1, a.device)
+        v = calculate_ssim_given_paths(a.path, a.img_size, a.batch_size or 1, a.device, device_resize=a.device_resize)
         print('SSIM: ', v[0], ' MS-SSIM: ', v[1])
     return v
 

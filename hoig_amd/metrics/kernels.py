@@ -119,6 +119,50 @@ def stage_images_u8(u8, size=None, steps=()):
     return y
 
 
+_pil_tables = {}   # (in, out, device) -> int32 [out, 2 + ksize] on the device
+
+
+def pil_table_host(n_in, n_out):
+    """hoig_pil_bilinear_table: the taps of one axis of Pillow's 8-bit BILINEAR resize, int32 numpy [n_out, 2 + ksize] with rows
+    [xmin, n, k[0..ksize)]."""
+    import numpy as np
+    ksize = L.lib.hoig_pil_bilinear_ksize(n_in, n_out)
+    L.check(min(ksize, 0), 'hoig_pil_bilinear_ksize')
+    table = np.zeros((n_out, 2 + ksize), np.int32)
+    L.call('hoig_pil_bilinear_table', n_in, n_out, ctypes.c_void_p(table.ctypes.data))
+    return table
+
+
+def _pil_table(n_in, n_out, device):
+    key = (n_in, n_out, torch.device(device))
+    if key not in _pil_tables:
+        _pil_tables[key] = torch.from_numpy(pil_table_host(n_in, n_out)).to(device)
+    return _pil_tables[key]
+
+
+def pil_resize_u8(u8, size):
+    """uint8 [B,H,W,3] on the device -> uint8 [B,Ho,Wo,3], size = (Ho, Wo): PIL's Image.resize((Wo, Ho), Image.BILINEAR) of every
+    image, equal in every byte.  One launch per axis that changes; the tap tables are made once per (in, out, device)."""
+    assert u8.dtype == torch.uint8 and u8.is_cuda and u8.is_contiguous() and u8.dim() == 4
+    B, H, W, C = u8.shape
+    Ho, Wo = size
+    nbytes = L.lib.hoig_resize_pil_bilinear_u8_workspace_bytes(B, H, W, C, Ho, Wo)
+    L.check(min(nbytes, 0), 'hoig_resize_pil_bilinear_u8_workspace_bytes')
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=u8.device)
+    tw = _pil_table(W, Wo, u8.device) if W != Wo else None
+    th = _pil_table(H, Ho, u8.device) if H != Ho else None
+    work = torch.empty(nbytes, dtype=torch.uint8, device=u8.device) if nbytes else None
+    L.call('hoig_resize_pil_bilinear_u8', O._p(u8), B, H, W, C, O._p(y), Ho, Wo, *[O._p(t) if t is not None else None
+                                                                                for t in (tw, th, work)], O._st())
+    return y
+
+
+def pil_resize_chain_u8(u8, img_size, side=299):
+    """images.resize_chain for a device batch: PIL BILINEAR to img_size x img_size, then to side x side."""
+    mid = u8 if tuple(u8.shape[1:3]) == (img_size, img_size) else pil_resize_u8(u8, (img_size, img_size))   # (a copy otherwise)
+    return pil_resize_u8(mid, (side, side))
+
+
 def nchw_to_nhwc(x):
     O._chk(x)
     return O.nchw_to_nhwc(x)

@@ -88,17 +88,25 @@ def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5,
     return v.mean() if size_average else v.mean(1)
 
 
-def calculate_ssim_given_paths(paths, img_size=256, batch_size=1, device=None):
+def ssim_pairs_u8(u8):
+    """Per-image (SSIM, MS-SSIM), each (N,), of uint8 [2N, 299, 299, 3] (X then Y, already through the resize chain) with
+    calculate_ssim_given_paths' inputs: ToTensor, ImageNet Normalize, data_range=255."""
+    xy = KR.stage_images_u8(u8, None, [(KR.IMAGENET_MEAN, KR.IMAGENET_STD)])
+    return ssim_nhwc(xy, 255).mean(1), ms_ssim_nhwc(xy, 255).mean(1)
+
+
+def calculate_ssim_given_paths(paths, img_size=256, batch_size=1, device=None, device_resize=False):
     """(SSIM, MS-SSIM) means over two directories of images paired by sorted position, with the reference's inputs exactly
     (metrics/ssim.py): get_eval_loader's transform (PIL resize to img_size, then to 299 x 299, ImageNet Normalize) and
     data_range=255 on those normalised tensors.  Their range is about 5, not 255, so C1 and C2 dominate and both values sit close to
-    1: that is the reference's setting, reproduced, not corrected."""
+    1: that is the reference's setting, reproduced, not corrected.  device_resize: the workers only decode and the two PIL resizes run
+    on the device (kernels.pil_resize_chain_u8: the same bytes, so the same values)."""
     from .lpips import paired_batches
     print('Calculating SSIM given paths %s and %s...' % (paths[0], paths[1]))
     dev = torch.device(device if device is not None else 'cuda')
     s_all, m_all = [], []
-    for u8 in I.DeviceBatches(paired_batches(paths, batch_size), dev, img_size):
-        xy = KR.stage_images_u8(u8, None, [(KR.IMAGENET_MEAN, KR.IMAGENET_STD)])
-        s_all.append(ssim_nhwc(xy, 255).mean(1))
-        m_all.append(ms_ssim_nhwc(xy, 255).mean(1))
+    for u8 in I.DeviceBatches(paired_batches(paths, batch_size), dev, None if device_resize else img_size):
+        s, m = ssim_pairs_u8(KR.pil_resize_chain_u8(u8, img_size) if device_resize else u8)
+        s_all.append(s)
+        m_all.append(m)
     return torch.cat(s_all).double().mean().item(), torch.cat(m_all).double().mean().item()

@@ -1,0 +1,151 @@
+"""Scoring eval output from device memory: FID, LPIPS and SSIM / MS-SSIM of a stream of generated / ground-truth uint8 batches, with
+the values the path functions give on two directories that hold the same images as PNGs.
+
+PNG is lossless and eval.py's bytes are made on the device (Trainer.eval_images_u8), so the only piece of the directory path without a
+device form was get_eval_loader's resize chain, PIL's 8-bit BILINEAR twice: kernels.pil_resize_chain_u8 gives the same bytes.  The
+values are then EQUAL, not close, as long as the same launches see the same bytes -- so the scorer re-groups whatever it is given into
+exactly the batches the path functions form (LPIPS is the mean of per-batch means, and a kernel may pick its tiling by batch size),
+keeps the remainder as uint8 and runs it as the short last batch when result() is asked.
+
+Every network is one the caller built (weights.py: without weights nothing runs).
+"""
+import numpy as np
+import torch
+
+from . import kernels as K
+from .fid import calculate_frechet_distance, compute_statistics_of_path
+from .ssim import ssim_pairs_u8
+
+
+class _Batches(object):
+    """Consecutive batches of exactly `size` images out of uint8 [N,H,W,3] pieces of any N; what is left over stays here."""
+
+    def __init__(self, size):
+        if size < 1:
+            raise ValueError('batch size must be >= 1')
+        self.size, self.rest = size, None
+
+    def push(self, u8):
+        """-> the full batches that `u8` completes, in order."""
+        if self.rest is not None:
+            if self.rest.shape[1:] != u8.shape[1:]:
+                raise ValueError('images of one batch differ in size: %s after %s' % (tuple(u8.shape[1:]), tuple(self.rest.shape[1:])))
+            u8 = torch.cat([self.rest, u8])
+        full = u8.shape[0] // self.size * self.size
+        self.rest = u8[full:].clone() if full < u8.shape[0] else None      # (a copy: the caller may reuse its tensor)
+        return [u8[i:i + self.size] for i in range(0, full, self.size)]
+
+
+class Scorer(object):
+    """``s = Scorer(fid=InceptionFeatures(...), lpips=LPIPS(...), ssim=True); s.update(gen_u8, gt_u8) ...; s.result()``
+
+    update(): device uint8 [N,H,W,3] of generated and ground-truth images, any N per call.  result(): {'n', 'fid', 'lpips', 'ssim',
+    'ms_ssim'} (absent metrics omitted), equal to calculate_fid_given_paths([gen, gt], fid_batch, ..), calculate_lpips_given_paths(
+    [gen, gt], img_size, lpips_batch, model=lpips) and calculate_ssim_given_paths([gen, gt], img_size, ssim_batch) on directories whose
+    sorted file names are in update() order.  FID is between the two streams, or against `fid_reference`: (mu, sigma) or an .npz of
+    them (then the ground truth's features are not taken)."""
+
+    def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None):
+        self.fid, self.lpips, self.ssim, self.img_size = fid, lpips, bool(ssim), img_size
+        self.n = 0
+        if isinstance(fid_reference, str):
+            if not fid_reference.endswith('.npz'):
+                raise ValueError('fid_reference %r: (mu, sigma) or an .npz of them' % fid_reference)
+            fid_reference = compute_statistics_of_path(fid_reference, None, None, None)
+        self.fid_reference = fid_reference
+        if fid is not None:
+            self._fid_gen, self._fid_gt = _Batches(fid_batch), (_Batches(fid_batch) if fid_reference is None else None)
+            self._feat_gen, self._feat_gt = [], []
+        # the pair metrics that share a batch size share the resized batch
+        self._pairs = {}
+        if lpips is not None:
+            self._pairs.setdefault(lpips_batch, []).append('lpips')
+        if self.ssim:
+            self._pairs.setdefault(ssim_batch, []).append('ssim')
+        self._pair_batches = {size: (_Batches(size), _Batches(size)) for size in self._pairs}
+        self._lpips_means, self._ssim, self._ms_ssim = [], [], []
+
+    # ---- one batch, as the path functions run it
+    def _features(self, u8):
+        return self.fid.features_u8(u8.contiguous()).double().cpu().numpy()
+
+    def _pair(self, metrics, gen, gt, into):
+        u8 = K.pil_resize_chain_u8(torch.cat([gen, gt]), self.img_size)
+        if 'lpips' in metrics:
+            into[0].append(self.lpips.distance_u8(u8).mean())
+        if 'ssim' in metrics:
+            s, m = ssim_pairs_u8(u8)
+            into[1].append(s)
+            into[2].append(m)
+
+    def update(self, gen_u8, gt_u8):
+        for t in (gen_u8, gt_u8):
+            if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 4 or t.shape[-1] != 3:
+                raise ValueError('device uint8 [N,H,W,3] expected, got %s %s on %s' % (t.dtype, tuple(t.shape), t.device))
+        if gen_u8.shape != gt_u8.shape:
+            raise ValueError('generated %s and ground truth %s differ in shape' % (tuple(gen_u8.shape), tuple(gt_u8.shape)))
+        self.n += gen_u8.shape[0]
+        if self.fid is not None:
+            self._feat_gen += [self._features(b) for b in self._fid_gen.push(gen_u8)]
+            if self._fid_gt is not None:
+                self._feat_gt += [self._features(b) for b in self._fid_gt.push(gt_u8)]
+        into = (self._lpips_means, self._ssim, self._ms_ssim)
+        for size, metrics in self._pairs.items():
+            bg, bt = self._pair_batches[size]
+            for gen, gt in zip(bg.push(gen_u8), bt.push(gt_u8)):
+                self._pair(metrics, gen, gt, into)
+
+    # ---- the totals: what was flushed plus the short last batch (the state is left as it is, so update() may go on)
+    def _statistics(self, feats, batches):
+        feats = list(feats)
+        if batches.rest is not None:
+            feats.append(self._features(batches.rest))
+        if not feats:
+            raise ValueError('no images were given')
+        act = np.concatenate(feats)
+        return np.mean(act, axis=0), np.cov(act, rowvar=False)
+
+    def statistics(self):
+        """(mu, sigma) of the generated set's Inception features (fid_score.py calculate_activation_statistics)."""
+        if self.fid is None:
+            raise ValueError('this scorer has no FID network')
+        return self._statistics(self._feat_gen, self._fid_gen)
+
+    def save_statistics(self, path):
+        """The .npz that fid.compute_statistics_of_path reads: mu, sigma of the generated set."""
+        mu, sigma = self.statistics()
+        np.savez(path, mu=mu, sigma=sigma)
+
+    def result(self):
+        if self.n == 0:
+            raise ValueError('no images were given')
+        out = {'n': self.n}
+        if self.fid is not None:
+            ref = self.fid_reference if self.fid_reference is not None else self._statistics(self._feat_gt, self._fid_gt)
+            out['fid'] = calculate_frechet_distance(*(self.statistics() + tuple(ref)))
+        into = (list(self._lpips_means), list(self._ssim), list(self._ms_ssim))
+        for size, metrics in self._pairs.items():
+            bg, bt = self._pair_batches[size]
+            if bg.rest is not None:
+                self._pair(metrics, bg.rest, bt.rest, into)
+        if self.lpips is not None:
+            out['lpips'] = torch.stack(into[0]).double().mean().item()
+        if self.ssim:
+            out['ssim'] = torch.cat(into[1]).double().mean().item()
+            out['ms_ssim'] = torch.cat(into[2]).double().mean().item()
+        return out
+
+
+def score_model(model, dataset, scorer, writer=None):
+    """The evaluation loop without files: for every batch of `dataset` (dicts as eval.py's loader yields them) forward() under
+    no_grad, the three images as device bytes, scorer.update(imitators, gt) and, with an EvalWriter, the PNGs of the same bytes.
+    Returns scorer.result()."""
+    for batch in dataset:
+        model.set_input(batch)
+        with torch.no_grad():
+            outs = model.forward()
+        images = model.eval_images_u8(outs)
+        scorer.update(images['imitators'], images['gt'])
+        if writer is not None:
+            writer.write_images(images, batch['nameA'], batch['nameB'])
+    return scorer.result()

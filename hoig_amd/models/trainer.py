@@ -709,6 +709,16 @@ class Trainer(BaseModel):
                 ('15_batch_fake_img', '_vis_batch_fake'), ('16_batch_src_img', '_vis_batch_src')]
         return OrderedDict((k, getattr(self, a)) for k, a in keys)
 
+    def eval_images_u8(self, forward_outputs):
+        """eval.py's three images of the current batch as device bytes: {'source', 'imitators', 'gt'} -> uint8 [B,H,W,3], from real_src,
+        the fake_tsf of `forward_outputs` (what forward() returned) and real_tsf.  The bytes are those of the crops eval.py takes from
+        '16_batch_src_img', '15_batch_fake_img' and '14_batch_real_img' (the same truncation, hoig_tensor2im_nhwc_u8), without
+        keep_data_for_visuals=True and without a host copy: what hoig_amd.metrics.stream.Scorer and EvalWriter.write_images take."""
+        n = self._n
+        fake_tsf = to_nhwc(forward_outputs[3]).detach()
+        return OrderedDict([('source', ops.tensor2im_nhwc_u8(n['real_src'])), ('imitators', ops.tensor2im_nhwc_u8(fake_tsf)),
+                            ('gt', ops.tensor2im_nhwc_u8(n['real_tsf']))])
+
     @staticmethod
     def _im(x_nhwc, idx=0, unnormalize=True):
         """utils/util.py:249-264 tensor2im: CHW uint8 of sample `idx`, or of the padding-0 grid when idx < 0."""

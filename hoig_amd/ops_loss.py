@@ -181,3 +181,11 @@ def tensor2im_u8(x_nhwc, nrow, unnormalize=True):
     out = torch.empty((C, nrw * H, ncol * W), dtype=torch.uint8, device=x_nhwc.device)
     L.call('hoig_tensor2im_u8', _p(x_nhwc.contiguous()), _p(out), B, H, W, C, nrow, 1 if unnormalize else 0, _st())
     return out
+
+
+def tensor2im_nhwc_u8(x_nhwc, unnormalize=True):
+    """The bytes of tensor2im_u8 sample by sample: uint8 [B,H,W,C] on the device (no grid, so nothing to crop)."""
+    x = x_nhwc.contiguous()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    L.call('hoig_tensor2im_nhwc_u8', _p(x), _p(out), x.numel(), 1 if unnormalize else 0, _st())
+    return out

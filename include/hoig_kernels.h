@@ -466,6 +466,9 @@ int hoig_stream_scratch_set(hoig_stream_t stream, void *ptr, int64_t bytes);
 /* eval.py output stage (utils/util.py:249-264): uint8 = (x+1)/2*255 truncated, NHWC fp32 -> CHW uint8 grid tile */
 int hoig_tensor2im_u8(const float *x, uint8_t *out, int B, int H, int W, int C, int nrow, int unnormalize,
                       hoig_stream_t stream);
+/* the same bytes without the grid: x [n] fp32 -> out [n] uint8 in x's own (NHWC, per-sample) layout, so that eval.py's three images
+ * can stay on the device (Trainer.eval_images_u8) */
+int hoig_tensor2im_nhwc_u8(const float *x, uint8_t *out, int64_t n, int unnormalize, hoig_stream_t stream);
 
 /* ---- input preparation AFTER the rasteriser (tensor stage): HandRecoveryFlow.forward
  *      (models/trainer.py:46-145) + the MANORenderer helpers it calls (utils/nmr.py:567-595, 874-968, 973-1100) +
@@ -623,6 +626,22 @@ int hoig_pool2d_fwd(const float *x, float *y, int B, int H, int W, int C, int k,
  * memory, n_affine x [sub[C] | div[C]] (read at the call: a captured launch keeps the values) */
 int hoig_stage_images_u8(const uint8_t *src, float *y, int B, int Hi, int Wi, int C, int Ho, int Wo, int n_affine, const float *affine,
                          hoig_stream_t stream);
+/* Pillow's 8-bit Image.resize((Wo, Ho), Image.BILINEAR) of every image of a batch, equal in every byte (what get_eval_loader applies
+ * twice before LPIPS and SSIM see an image; hoig_amd/csrc/pil_resize.h states the fixed-point algorithm): uint8 [B,H,W,3] ->
+ * [B,Ho,Wo,3], along W first, then along H on the rounded bytes; a pass that keeps its size is skipped.  C != 3 or a size outside
+ * 1..4096: HOIG_EINVAL.
+ * hoig_pil_bilinear_ksize / _table (HOST, no HIP call): the taps of one axis for in -> out samples, `out` rows of 2 + ksize int32:
+ *   [xmin, n, k[0..ksize)], n <= ksize = 2 ceil(max(in / out, 1)) + 1 taps of 22 fractional bits on src[xmin .. xmin + n).
+ * hoig_resize_pil_bilinear_u8_host (HOST twin, the same tap code, no HIP call): src, dst in host memory.
+ * hoig_resize_pil_bilinear_u8: src, dst, table_w (W -> Wo), table_h (H -> Ho), workspace in device memory; a table may be NULL when
+ *   its pass is skipped, the workspace (hoig_resize_pil_bilinear_u8_workspace_bytes: the rows of the first pass's result that the
+ *   second reads; 0 unless both passes run) when that is 0.  dst and workspace 4-byte aligned.  One launch per pass. */
+int hoig_pil_bilinear_ksize(int in, int out);
+int hoig_pil_bilinear_table(int in, int out, int32_t *table);
+int64_t hoig_resize_pil_bilinear_u8_workspace_bytes(int B, int H, int W, int C, int Ho, int Wo);
+int hoig_resize_pil_bilinear_u8_host(const uint8_t *src, int B, int H, int W, int C, uint8_t *dst, int Ho, int Wo);
+int hoig_resize_pil_bilinear_u8(const uint8_t *src, int B, int H, int W, int C, uint8_t *dst, int Ho, int Wo, const int32_t *table_w,
+                                const int32_t *table_h, void *workspace, hoig_stream_t stream);
 /* zero-padded copy [B,H,W,C] -> [B,H+2pad_h,W+2pad_w,C] (the asymmetric paddings of Inception's 1x7 / 7x1 / 1x3 / 3x1 layers, which
  * then run on hoig_conv2d_fwd with pad 0); C % 4 == 0, HOIG_EUNSUPPORTED otherwise */
 int hoig_pad2d(const float *x, float *y, int B, int H, int W, int C, int pad_h, int pad_w, hoig_stream_t stream);

@@ -1,6 +1,8 @@
 """Steady-state throughput of hoig_amd.metrics on seeded weights (the real weight files are not needed to time the networks):
 FID Inception features (device-only from staged uint8 batches, and path-fed from PNG directories), LPIPS pairs, SSIM + MS-SSIM
-pairs; achieved TF/s of the two networks from the multiply-adds their layer tables give (2 FLOP per multiply-add).
+pairs; achieved TF/s of the two networks from the multiply-adds their layer tables give (2 FLOP per multiply-add).  Then the pieces
+of scoring from device memory, in the same run: the two launches of the PIL-exact resize alone, the path functions with that resize
+on the device against on the host, and hoig_amd.metrics.stream.Scorer fed from device tensors.
 usage: python tools/bench_metrics.py [--batch 50] [--iters 10] [--images 200] [--out FILE]"""
 import argparse
 import os
@@ -20,6 +22,7 @@ from hoig_amd.metrics import kernels as K                  # noqa: E402
 from hoig_amd.metrics.fid import InceptionFeatures, get_activations   # noqa: E402
 from hoig_amd.metrics.lpips import LPIPS, calculate_lpips_given_paths, paired_batches   # noqa: E402
 from hoig_amd.metrics.ssim import ms_ssim_nhwc, ssim_nhwc, calculate_ssim_given_paths  # noqa: E402
+from hoig_amd.metrics.stream import Scorer               # noqa: E402
 
 
 def timed(fn, iters):
@@ -77,6 +80,15 @@ def main():
     t = timed(lambda: (ssim_nhwc(xy, 255), ms_ssim_nhwc(xy, 255)), a.iters)
     say('SSIM + MS-SSIM at 299: device-only %.2f ms per batch = %.0f pairs/s' % (t * 1e3, B / t))
 
+    pair = torch.cat([u8, u8.flip(0)])                                  # [2B,256,256,3]: one batch of B pairs
+    wide = K.pil_resize_u8(pair, (256, 299))
+    t_w = timed(lambda: K.pil_resize_u8(pair, (256, 299)), a.iters)
+    t_h = timed(lambda: K.pil_resize_u8(wide, (299, 299)), a.iters)
+    t = timed(lambda: K.pil_resize_chain_u8(pair, 256), a.iters)
+    moved = (pair.numel() + 2 * wide.numel() + wide.numel() // 256 * 299) / 1e6
+    say('PIL-exact resize 256 -> 299 of %d pairs: along W %.3f ms, along H %.3f ms (each launch alone), the chain %.3f ms per batch = '
+        '%.0f pairs/s (%.1f MB read and written, %.0f GB/s)' % (B, t_w * 1e3, t_h * 1e3, t * 1e3, B / t, moved, moved / 1e3 / t))
+
     with tempfile.TemporaryDirectory() as root:
         da, db = os.path.join(root, 'a'), os.path.join(root, 'b')
         fa = R.write_pngs(da, a.images, 256, 1)
@@ -107,6 +119,37 @@ def main():
         calculate_ssim_given_paths([da, db], 256, B)
         t = time.perf_counter() - t0
         say('SSIM + MS-SSIM path-fed: %d pairs in %.2f s = %.0f pairs/s' % (len(fa), t, len(fa) / t))
+        t0 = time.perf_counter()
+        calculate_lpips_given_paths([da, db], 256, B, model=lp, device_resize=True)
+        t = time.perf_counter() - t0
+        say('LPIPS path-fed, device_resize=True: %d pairs in %.2f s = %.0f pairs/s' % (len(fa), t, len(fa) / t))
+        t0 = time.perf_counter()
+        calculate_ssim_given_paths([da, db], 256, B, device_resize=True)
+        t = time.perf_counter() - t0
+        say('SSIM + MS-SSIM path-fed, device_resize=True: %d pairs in %.2f s = %.0f pairs/s' % (len(fa), t, len(fa) / t))
+        gen = torch.cat(list(I.DeviceBatches(I.batches_of(fa, B), 'cuda')))
+        gt = torch.cat(list(I.DeviceBatches(I.batches_of(I.list_images(db), B), 'cuda')))
+
+    # the same images from device memory, in updates of 32 (not the metrics' batch), after one warm-up pass; result() apart: with FID it
+    # is the host's fp64 sqrtm of a dims x dims product (fid_score.py), which the path-fed feature rate above does not contain either
+    def stream(**kw):
+        def run():
+            s = Scorer(fid=kw.get('fid'), lpips=kw.get('lpips'), ssim=kw.get('ssim', False), fid_batch=B, lpips_batch=B, ssim_batch=B)
+            t0 = time.perf_counter()
+            for i in range(0, gen.shape[0], 32):
+                s.update(gen[i:i + 32], gt[i:i + 32])
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            s.result()
+            return t1 - t0, time.perf_counter() - t1
+        run()
+        return run()
+
+    n = gen.shape[0]
+    for label, kw in (('FID features (both streams: 2 images per pair)', dict(fid=inc)), ('LPIPS', dict(lpips=lp)),
+                      ('SSIM + MS-SSIM', dict(ssim=True)), ('FID + LPIPS + SSIM + MS-SSIM', dict(fid=inc, lpips=lp, ssim=True))):
+        t, tr = stream(**kw)
+        say('Scorer.update from device memory, %s: %d pairs in %.3f s = %.0f pairs/s; result() %.3f s' % (label, n, t, n / t, tr))
     if a.out:
         with open(a.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
