@@ -205,6 +205,10 @@ def _load():
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]
     lib.hoig_jpeg_decode_par_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_conv_last_route.argtypes = [_i]
+    lib.hoig_conv_last_route.restype = ctypes.c_int
+    lib.hoig_conv_route_name.argtypes = [_i]
+    lib.hoig_conv_route_name.restype = ctypes.c_char_p
     lib.hoig_version.argtypes = []
     lib.hoig_version.restype = ctypes.c_char_p
     return lib
@@ -224,6 +228,29 @@ def set_tuning(key, value):
 # HOIG_TUNING="key=value,key=value": variant choices for A/B runs (bench.py and the tools set them through this one variable)
 for _kv in filter(None, os.environ.get('HOIG_TUNING', '').split(',')):
     set_tuning(*_kv.split('='))
+
+
+ROUTE_FWD, ROUTE_DGRAD, ROUTE_WGRAD = 0, 1, 2
+
+
+def route_names():
+    """The library's table of convolution routes (hoig_amd/csrc/conv_route.h), by id."""
+    names, i = [], 0
+    while True:
+        n = lib.hoig_conv_route_name(i)
+        if n is None:
+            return names
+        names.append(n.decode())
+        i += 1
+
+
+def last_route(which):
+    """hoig_conv_last_route: the name of the convolution launcher that ran last on this thread (0 forward, 1 data gradient,
+    2 weight gradient; 'none' before the first)."""
+    rid = lib.hoig_conv_last_route(int(which))
+    if rid < 0:
+        raise ValueError('last_route(%r): 0 forward, 1 data gradient, 2 weight gradient' % (which,))
+    return lib.hoig_conv_route_name(rid).decode()
 
 
 def check(rc, what):

@@ -396,6 +396,8 @@ int launch_flat_m16(FlatArgs a, int ns, hipStream_t st) {
     split = (int)hoig_cdiv(steps, a.steps_per_split);
     dim3 grid(a.nblk, split);
     if (split > 1 && hipMemsetAsync(a.C, 0, (size_t)a.Bn * a.Hd * a.Wd * a.N * sizeof(float), st) != hipSuccess) return HOIG_ELAUNCH;
+    if (KS == 3) HOIG_ROUTE_FD(a.f16, flat_m16_k3);
+    else HOIG_ROUTE_FD(a.f16, flat_m16_k5);
     return KS == 3 ? launch_ks<3>(a, ns, grid, shm, split > 1, st) : launch_ks<5>(a, ns, grid, shm, split > 1, st);
 }
 

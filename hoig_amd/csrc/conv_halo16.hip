@@ -675,6 +675,8 @@ int launch_one(const HaloArgs &a, hipStream_t st) {
         if constexpr (NS == 2) return HOIG_EUNSUPPORTED;
         else {
             if (a.f16 || a.A2) return HOIG_EUNSUPPORTED;
+            if (a.b_split > 0) BN == 64 ? HOIG_ROUTE_D(halo3_m16_64_split_pair) : HOIG_ROUTE_D(halo3_m16_128_split_pair);
+            else BN == 64 ? HOIG_ROUTE_D(halo3_m16_64_split) : HOIG_ROUTE_D(halo3_m16_128_split);
             static hoig_once once_s;
             if (!once_s.done()) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, false, true>),
@@ -699,6 +701,7 @@ int launch_one(const HaloArgs &a, hipStream_t st) {
     }
     if (a.in_scale) {                                      // inference chain: norm + ReLU of the gathered tensor applied in the loader
         if (!a.f16 || a.N % BN || !a.in_shift || a.b_split > 0) return HOIG_EUNSUPPORTED;
+        BN == 64 ? HOIG_ROUTE_F(halo3_m16_64_normin) : HOIG_ROUTE_F(halo3_m16_128_normin);
         static hoig_once once_n;
         if (!once_n.done()) {
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true, true>),
@@ -710,6 +713,9 @@ int launch_one(const HaloArgs &a, hipStream_t st) {
         HOIG_LAUNCH_CHECK();
         return HOIG_OK;
     }
+    if (a.b_split > 0 && a.f16) BN == 64 ? HOIG_ROUTE_F(halo3_m16_64_pair) : HOIG_ROUTE_F(halo3_m16_128_pair);
+    else if (BN == 64) HOIG_ROUTE_FD(a.f16, halo3_m16_64);
+    else HOIG_ROUTE_FD(a.f16, halo3_m16_128);
     if (hoig_tuning(HOIG_TUNE_WDMA16) != 0 && a.N % BN == 0) {       // weight tiles by LDS-DMA (whole channel tiles only)
         static hoig_once once_d;
         if (!once_d.done()) {
@@ -747,6 +753,8 @@ int launch_s2(const HaloArgs &a, int ns, hipStream_t st) {
     const bool rows8_ok = a.nblk >= 512 && !(a.tiles_y & 1) && a.N % 128 == 0;
     if (rows8_ok && (pipe == 1 || pipe == 3)) return launch_halo_s2_m16p(a, ns, SCATTER, true, st);
     if (pipe == 2 || (pipe != 0 && a.nblk <= 256)) return launch_halo_s2_m16p(a, ns, SCATTER, false, st);
+    if (n64) SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_m16_64) : HOIG_ROUTE_FD(a.f16, s2g_m16_64);
+    else SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_m16_128) : HOIG_ROUTE_FD(a.f16, s2g_m16_128);
     if (n64) {
         if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 64, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
         else HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 64, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));

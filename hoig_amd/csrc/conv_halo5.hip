@@ -290,6 +290,8 @@ int launch_one(const FlatArgs &a, dim3 grid, hipStream_t st) {
             return HOIG_ELAUNCH;
         once.set();
     }
+    if (SPLITK) HOIG_ROUTE_FD(F16, halo5_m16_ksplit);
+    else HOIG_ROUTE_FD(F16, halo5_m16);
     conv_halo5_m16_kernel<NSX, F16, SPLITK, TPS><<<grid, NT, shm, st>>>(a);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;

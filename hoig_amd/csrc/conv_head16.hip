@@ -191,6 +191,7 @@ int launch_head7(const hoig_conv_desc *d, const float *x, const float *w, const 
         attr.set();
     }
     const int n_strips = (d->Wi + H7_OUTW - 1) / H7_OUTW, n_chunks = (d->Hi + H7_TH - 1) / H7_TH;
+    HOIG_ROUTE_F(head7);
     conv_head7_m16_kernel<CO, KSTEPS><<<d->B * n_chunks * n_strips, H7_THREADS, lds, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, acts, d->slope,
                                                                                    n_strips, n_chunks);
     HOIG_LAUNCH_CHECK();

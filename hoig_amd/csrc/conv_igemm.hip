@@ -532,6 +532,12 @@ int launch_igemm(IgemmArgs a, bool ncontig, hipStream_t st) {
     enable_phase_major(a.g, BM, a.g.Cg % 32 == 0);
     const bool vec = (a.g.Cg % 4 == 0);
     dim3 grid(a.nblk), block(256);
+    // (ncontig: the data gradient's weight layout -- hoig_conv2d_bwd_data is its only caller)
+    if (BN == 32) HOIG_ROUTE_FD(!ncontig, igemm_f32_128x32);
+    else if (BM == 128 && BN == 64) HOIG_ROUTE_FD(!ncontig, igemm_f32_128x64);
+    else if (BN == 64) HOIG_ROUTE_FD(!ncontig, igemm_f32_64x64);
+    else if (BM == 128) HOIG_ROUTE_FD(!ncontig, igemm_f32_128x128);
+    else HOIG_ROUTE_FD(!ncontig, igemm_f32_64x128);
     if (vec) {
         if (ncontig) igemm_f32_kernel<BM, BN, WM, WN, 4, true><<<grid, block, 0, st>>>(a);
         else igemm_f32_kernel<BM, BN, WM, WN, 4, false><<<grid, block, 0, st>>>(a);
@@ -662,6 +668,11 @@ static int launch_wgrad(WgradArgs a, hipStream_t st) {
     a.m_per_split = mps;
     splits = (int)hoig_cdiv(a.M, mps);
     dim3 grid(a.nblk_mn, splits), block(256);
+    if (BM == 32 && BN == 64) HOIG_ROUTE_W(wgrad_f32_32x64);
+    else if (BM == 32) HOIG_ROUTE_W(wgrad_f32_32x128);
+    else if (BM == 64) HOIG_ROUTE_W(wgrad_f32_64x128);
+    else if (BN == 64) HOIG_ROUTE_W(wgrad_f32_128x64);
+    else HOIG_ROUTE_W(wgrad_f32_128x128);
     if (a.g.Cg % 4 == 0) wgrad_f32_kernel<BM, BN, WM, WN, 4><<<grid, block, 0, st>>>(a);
     else wgrad_f32_kernel<BM, BN, WM, WN, 1><<<grid, block, 0, st>>>(a);
     HOIG_LAUNCH_CHECK();

@@ -277,6 +277,10 @@ int launch(Args a, int ns, hipStream_t st) {
         }
     }
     dim3 grid(a.nblk, a.ksplit);
+    if (BM == 128 && BN == 128) WN == 4 ? HOIG_ROUTE_FD(a.f16, igemm_m16_128x128w) : HOIG_ROUTE_FD(a.f16, igemm_m16_128x128);
+    else if (BN == 128) HOIG_ROUTE_FD(a.f16, igemm_m16_64x128);
+    else if (BM == 128) HOIG_ROUTE_FD(a.f16, igemm_m16_128x64);
+    else HOIG_ROUTE_FD(a.f16, igemm_m16_64x64);
     if (a.ksplit > 1) {
         if (a.f16) HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, true, true><<<grid, NT, 0, st>>>(a));
         else HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, false, true><<<grid, NT, 0, st>>>(a));

@@ -483,6 +483,10 @@ int launch(Args a, int ns, hipStream_t st) {
         }
     }
     dim3 grid(a.nblk, a.ksplit);
+    if (BM == 128 && BN == 128) WN == 4 ? HOIG_ROUTE_FD(a.f16, igemm_bf16_128x128w) : HOIG_ROUTE_FD(a.f16, igemm_bf16_128x128);
+    else if (BN == 128) HOIG_ROUTE_FD(a.f16, igemm_bf16_64x128);
+    else if (BM == 128) HOIG_ROUTE_FD(a.f16, igemm_bf16_128x64);
+    else HOIG_ROUTE_FD(a.f16, igemm_bf16_64x64);
     if (a.f16) HOIG_NS_SWITCH(ns, igemm_bf16_kernel<BM, BN, WM, WN, NSX, BK, true><<<grid, NT, 0, st>>>(a));
     else HOIG_NS_SWITCH(ns, igemm_bf16_kernel<BM, BN, WM, WN, NSX, BK, false><<<grid, NT, 0, st>>>(a));
     HOIG_LAUNCH_CHECK();
@@ -1019,6 +1023,9 @@ int launch_halo3_one(const HaloArgs &a, hipStream_t st) {
             return HOIG_ELAUNCH;
         once.set();
     }
+    if (BN == 64) HOIG_ROUTE_FD(a.f16, halo3_64);
+    else if (MODE == 1) HOIG_ROUTE_FD(a.f16, halo3_128w);
+    else HOIG_ROUTE_FD(a.f16, halo3_128);
     if (a.f16) conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
     else conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, false><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
     HOIG_LAUNCH_CHECK();
@@ -1367,6 +1374,8 @@ int launch_halo_s2(HaloArgs a, int ns, hipStream_t st) {
     // 64-channel tiles (ConvTranspose2d 128 -> 64 forward at full resolution: -5 %; the two-term data gradient of the same
     // shape: +24 %), which stay on the 32x32 kernel
     if (hoig_tuning(HOIG_TUNE_S2_16) != 0 && !(SCATTER && n64 && ns == 2)) return launch_halo_s2_m16(a, ns, SCATTER, st);
+    if (n64) SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_64) : HOIG_ROUTE_FD(a.f16, s2g_64);
+    else SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_128) : HOIG_ROUTE_FD(a.f16, s2g_128);
     if (n64) {
         if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 64, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
         else HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 64, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));
@@ -1385,14 +1394,16 @@ int launch_halo(HaloArgs a, int ns, hipStream_t st) {
     const bool n64 = (a.N % 128) != 0;        // 64-channel layers (the full-resolution levels, VGG conv1): BN = 64 tiles
     a.nblk_n = (int)hoig_cdiv(a.N, n64 ? 64 : 128);
     a.nblk = a.Bn * a.tiles_x * a.tiles_y * a.nblk_n;
+    const bool wide = a.nblk < 384;
+    if (KS == 1) n64 ? HOIG_ROUTE_FD(a.f16, halo1_64) : (wide ? HOIG_ROUTE_FD(a.f16, halo1_128w) : HOIG_ROUTE_FD(a.f16, halo1_128));
+    else n64 ? HOIG_ROUTE_FD(a.f16, same5_64) : (wide ? HOIG_ROUTE_FD(a.f16, same5_128w) : HOIG_ROUTE_FD(a.f16, same5_128));
     if (n64) {
         if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 64, true><<<a.nblk, 256, 0, st>>>(a));
         else HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 64, false><<<a.nblk, 256, 0, st>>>(a));
         HOIG_LAUNCH_CHECK();
         return HOIG_OK;
     }
-    // fewer than ~1.5 workgroups per CU: 8 waves per workgroup keep two waves on every SIMD
-    const bool wide = a.nblk < 384;
+    // fewer than ~1.5 workgroups per CU (wide): 8 waves per workgroup keep two waves on every SIMD
     if (wide) {
         if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 4, 128, true><<<a.nblk, 512, 0, st>>>(a));
         else HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 4, 128, false><<<a.nblk, 512, 0, st>>>(a));

@@ -355,6 +355,9 @@ int launch_s2p_one(const HaloArgs &a, hipStream_t st) {
             return HOIG_ELAUNCH;
         once.set();
     }
+    if (WM == 4) SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p8_128) : HOIG_ROUTE_FD(F16, s2g_m16p8_128);
+    else if (BN == 64) SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p4_64) : HOIG_ROUTE_FD(F16, s2g_m16p4_64);
+    else SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p4_128) : HOIG_ROUTE_FD(F16, s2g_m16p4_128);
     conv_halo_s2_m16p_kernel<NSX, BN, SCATTER, F16, WM><<<a.nblk, 128 * WM, shm, st>>>(a);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;

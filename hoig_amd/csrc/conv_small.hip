@@ -349,6 +349,7 @@ int hoig_conv_small_fwd_acts(const hoig_conv_desc *d, const float *x, const floa
     const int tiles = d->B * (int)hoig_cdiv(d->Hi, F4_TH) * (int)hoig_cdiv(d->Wi, F4_TW);
 #define HOIG_SMALL_FWD(N)                                                                                          \
     conv_small_fwd4_kernel<N><<<tiles, 256, 0, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->pad, acts, d->slope, d->Co)
+    HOIG_ROUTE_F(small);
     switch (d->Co) {
         case 1: HOIG_SMALL_FWD(1); break;
         case 2: HOIG_SMALL_FWD(2); break;
@@ -383,6 +384,7 @@ int hoig_conv_small_ci_fwd(const hoig_conv_desc *d, const float *x, const float 
 #define HOIG_SMALL_CF(N) \
     conv_small_dgrad4_kernel<N, true><<<grid, 256, 0, st>>>(x, w, y, d->B, d->Hi, d->Wi, d->Co, d->pad, d->Ci, off,       \
                                                             off > 0 ? 1 : 0, bb, act, d->slope)
+        HOIG_ROUTE_F(small_ci);
         switch (n) {
             case 1: HOIG_SMALL_CF(1); break;
             case 2: HOIG_SMALL_CF(2); break;
@@ -402,6 +404,7 @@ int hoig_conv_small_dgrad(const hoig_conv_desc *d, const float *dy, const float 
 #define HOIG_SMALL_DG(N) \
     conv_small_dgrad4_kernel<N, false><<<grid, 256, 0, st>>>(dy, w, dx, d->B, d->Hi, d->Wi, d->Ci, d->pad, d->Co, 0, 0, \
                                                              nullptr, 0, 0.f)
+    HOIG_ROUTE_D(small);
     switch (d->Co) {
         case 1: HOIG_SMALL_DG(1); break;
         case 2: HOIG_SMALL_DG(2); break;
@@ -423,6 +426,7 @@ int hoig_conv_small_wgrad(const hoig_conv_desc *d, const float *x, const float *
     dim3 grid((unsigned)hoig_cdiv(tiles, tpb), d->Ci / CC);
 #define HOIG_SMALL_WG(N) \
     conv_small_wgrad_kernel<N><<<grid, 256, 0, st>>>(x, dy, dw, d->B, d->Hi, d->Wi, d->Ci, d->R, d->S, d->pad, d->Co, tpb)
+    HOIG_ROUTE_W(wgrad_small);
     switch (d->Co) {
         case 1: HOIG_SMALL_WG(1); break;
         case 2: HOIG_SMALL_WG(2); break;
@@ -486,6 +490,7 @@ int hoig_conv_dot_fwd(const hoig_conv_desc *d, const float *x, const float *w, c
 #define HOIG_DOT_FWD(N)                                                                                                    \
     conv_dot_fwd_kernel<N><<<grid, 256, 0, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->Ho, d->Wo, d->R, d->S, d->stride, \
                                                  d->pad, d->act, d->slope)
+    HOIG_ROUTE_F(dot);
     switch (d->Co) {
         case 1: HOIG_DOT_FWD(1); break;
         case 2: HOIG_DOT_FWD(2); break;

@@ -672,6 +672,7 @@ int launch_gemm(const ThinArgs &a, int precision, hipStream_t st) {
     const size_t smem = (size_t)nw * 64 * (a.KP + 8) * 2 + (size_t)a.KP * 2 + (size_t)nt * a.F * a.HR * a.CW * 2;
     if (smem > 160 * 1024) return HOIG_EUNSUPPORTED;
     dim3 grid((unsigned)hoig_cdiv(a.ntiles, a.strip), a.CD / 64);
+    HOIG_ROUTE_FD(FP16, thin);                      // (FP16: the forward's operand format; the data gradient runs on bf16)
 #define HOIG_THIN_GEMM(NT_, NW_)                                                                                         \
     do {                                                                                                                 \
         static hoig_once attr;                                                                                        \
@@ -782,6 +783,8 @@ int hoig_conv_thin_wgrad(const hoig_conv_desc *d, const float *x, const float *d
     while (nwg > 64 && (size_t)nwg * groups * 64 * a.NP * 4 > WS_SLOT_BYTES) nwg >>= 1;
     dim3 grid(nwg, groups);
     a.Ws = nwg > 8 ? thin_workspace(st, (size_t)nwg * groups * 64 * a.NP * 4) : nullptr;
+    if (thin_in) a.Ws ? HOIG_ROUTE_W(wgrad_thin_in_ws) : HOIG_ROUTE_W(wgrad_thin_in_direct);
+    else a.Ws ? HOIG_ROUTE_W(wgrad_thin_out_ws) : HOIG_ROUTE_W(wgrad_thin_out_direct);
     int rc;
     if (nfr == 1) rc = launch_wgrad_t<1, 1>(a, nt, nd, grid, smem, st);
     else if (nfr == 2) rc = launch_wgrad_t<2, 1>(a, nt, nd, grid, smem, st);
@@ -820,6 +823,7 @@ int hoig_conv_thin_out(const hoig_conv_desc *d, const float *x, const float *w, 
     const size_t smem = (size_t)nw * (CD / 64) * F * KK * 144 + (size_t)nd * a.HR * a.HWc * 80;
     if (smem > 160 * 1024) return HOIG_EUNSUPPORTED;
     const unsigned grid = (unsigned)hoig_cdiv(a.ntiles, a.strip);
+    HOIG_ROUTE_FD(!dgrad, thin_out);
 #define HOIG_THIN_OUT(FP16_, ND_, NW_)                                                                                   \
     do {                                                                                                                 \
         static hoig_once attr;                                                                                        \

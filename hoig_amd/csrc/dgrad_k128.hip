@@ -121,6 +121,7 @@ int launch_dgrad_thin(const float *dy, const unsigned short *wh, const unsigned 
             return HOIG_ELAUNCH;
         once.set();
     }
+    HOIG_ROUTE_D(k128);
     HOIG_NS_SWITCH(ns, dgrad_thin_k128_kernel<NSX><<<dim3(mtiles, split), 256, shm, st>>>(a));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;

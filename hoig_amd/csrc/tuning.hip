@@ -2,6 +2,7 @@
 #include <cstring>
 #include "hoig_kernels.h"
 #include "tuning.h"
+#include "conv_route.h"
 
 namespace {
 struct Entry {
@@ -39,4 +40,25 @@ extern "C" int hoig_set_tuning(const char *key, int value) {
             return prev;
         }
     return -1;
+}
+
+// the route record (conv_route.h): the launcher that ran last on this thread, per pass
+thread_local int hoig_route_last[3] = {0, 0, 0};
+
+extern "C" int hoig_conv_last_route(int which) { return (which >= 0 && which < 3) ? hoig_route_last[which] : -1; }
+
+extern "C" const char *hoig_conv_route_name(int id) {
+    static const char *const names[HOIG_ROUTE_COUNT] = {
+        "none",
+#define HOIG_R_W(n) #n,
+#define HOIG_R_D(n) "dgrad_" #n,
+#define HOIG_R_F(n) "fwd_" #n,
+#define HOIG_R_FD(n) "fwd_" #n, "dgrad_" #n,
+        HOIG_CONV_ROUTES(HOIG_R_W, HOIG_R_D, HOIG_R_F, HOIG_R_FD)
+#undef HOIG_R_W
+#undef HOIG_R_D
+#undef HOIG_R_F
+#undef HOIG_R_FD
+    };
+    return (id >= 0 && id < HOIG_ROUTE_COUNT) ? names[id] : nullptr;
 }

@@ -303,6 +303,8 @@ int launch_wgrad_dma(const WHaloArgs &a, int ns, dim3 grid, hipStream_t st) {
             return HOIG_ELAUNCH;
         once.set();
     }
+    if (a.b_split > 0) HOIG_ROUTE_W(wgrad_dma_pair);
+    else HOIG_ROUTE_W(wgrad_dma);
     if (ns == 3) wgrad_dma_kernel<2><<<grid, D_NT, wgrad_dma_lds(2), st>>>(a);
     else wgrad_dma_kernel<1><<<grid, D_NT, wgrad_dma_lds(1), st>>>(a);
     HOIG_LAUNCH_CHECK();

@@ -369,6 +369,7 @@ int launch_wgrad_tile5(WFlatArgs a, int Bn, int ns, hipStream_t st) {
     }
     static_assert(tile5_lds(2) <= 160 * 1024, "both double-buffered images must fit in LDS");
     dim3 grid(a.nblk, splits);
+    HOIG_ROUTE_W(wgrad_tile5);
     HOIG_NS_SWITCH(ns, wgrad_tile5_kernel<NSX><<<grid, NT, tile5_lds(NSX), st>>>(a));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
@@ -404,6 +405,7 @@ int launch_wgrad_flat5(const float *x, const float *dy, float *dw, float *dbias,
         once.set();
     }
     dim3 grid(a.nblk, splits);
+    HOIG_ROUTE_W(wgrad_flat5);
     HOIG_NS_SWITCH(ns, wgrad_flat_kernel<NSX><<<grid, NT, shm, st>>>(a));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;

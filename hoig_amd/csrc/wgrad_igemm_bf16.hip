@@ -260,6 +260,8 @@ int launch_wgrad_bf16(WArgs a, int ns, hipStream_t st) {
     a.m_per_split = mps;
     splits = (int)hoig_cdiv(a.M, mps);
     dim3 grid(a.nblk_mn, splits);
+    if (BM == 64) HOIG_ROUTE_W(wgrad_bf16_64);
+    else HOIG_ROUTE_W(wgrad_bf16_128);
     HOIG_NS_SWITCH(ns, wgrad_bf16_kernel<BM, NSX><<<grid, 256, 0, st>>>(a));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
@@ -576,6 +578,11 @@ int launch_wgrad_halo(const hoig_conv_desc *d, const float *x, const float *dy, 
     splits = (int)hoig_cdiv(a.n_mtiles, a.mt_per_split);
     dim3 grid(a.nblk, splits);
     if (dy_split) return launch_wgrad_dma(a, ns, grid, st);
+    if (th4) HOIG_ROUTE_W(wgrad_halo_th4);
+    else if (a.tout) HOIG_ROUTE_W(wgrad_halo_tout);
+    else if (s2) cm == 2 ? HOIG_ROUTE_W(wgrad_halo_s2_cm2) : HOIG_ROUTE_W(wgrad_halo_s2_cm1);
+    else if (d->R == 5) HOIG_ROUTE_W(wgrad_halo_5x5);
+    else cm == 2 ? HOIG_ROUTE_W(wgrad_halo_cm2) : HOIG_ROUTE_W(wgrad_halo_cm1);
     if (th4) {
         constexpr int LDS4 = 2 * (4 * 32 * 320) + (((6 * 34 * 64) + 255) / 256) * 256;      // dy hi, lo | x hi
         static hoig_once once;

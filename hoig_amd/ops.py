@@ -703,7 +703,7 @@ class _Conv(Function):
             return _Conv._backward_split(ctx, dy, dxr, x, w)
         dw_ret = db_ret = None
         db, ret_b = None, False
-        if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2]:
+        if ctx.has_bias and ctx.needs_input_grad[2]:              # (also under a frozen weight: no weight-gradient launch then)
             db, ret_b = _grad_target(b)
             db_ret = db if ret_b else None
         if d.act != L.ACT_NONE:
@@ -720,6 +720,8 @@ class _Conv(Function):
             _wgrad_launch(x.device, ret_w or (db is not None and ret_b), (x, g),
                           'hoig_conv2d_bwd_weight', ctx.d_wg, _p(x), _p(g), _p(dw), _p(db))
             dw_ret = dw if ret_w else None
+        elif db is not None:                # a live bias under a frozen weight: its gradient is the column sum of g, on its own
+            L.call('hoig_colsum_accum', _p(g), _p(db), g.numel() // d.Co, d.Co, _st())
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)

@@ -593,6 +593,14 @@ const char *hoig_version(void);
  * Process-wide, not synchronised: set before launching. */
 int hoig_set_tuning(const char *key, int value);
 
+/* The route record: which convolution launcher ran last on the calling host thread.  Every convolution launcher stores its id (one
+ * thread-local integer per pass, hoig_amd/csrc/conv_route.h) immediately before its kernel launch; nothing on the device changes and a
+ * stream capture records the same ids.  which: 0 forward, 1 data gradient, 2 weight gradient -> the id (0: none yet; -1: bad `which`).
+ * hoig_conv_route_name(id): "wgrad_halo_cm2", "dgrad_halo3_m16_128", ... for 0 <= id < the number of routes, NULL beyond: walk the
+ * ids from 0 until NULL for the whole table.  The tests assert with it that a shape ran on the kernel it was chosen for. */
+int hoig_conv_last_route(int which);
+const char *hoig_conv_route_name(int id);
+
 /* ---- MANO hand layer: pose / shape parameters -> skinned hand vertices, the step in front of the rasteriser.
  *      Replaces, for this path, smplx 0.1.28's MANO layer (HOIG_HOv3/models/networks/hmr.py:55,84-85: `mano_layer_right(global_orient,
  *      hand_pose, betas, transl).vertices`, use_pca=False, flat_hand_mean=True) and manopth's ManoLayer (HOIG_DexYCB/models/networks/
