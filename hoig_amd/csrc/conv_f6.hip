@@ -556,13 +556,23 @@ static int launch_f6(const hoig_conv_desc *d, const float *x, const float *x2, i
                 return HOIG_ELAUNCH;
             once_n.set();
         }
-        if (n64) conv_halo3_f6_kernel<64, true><<<a.nblk, NT, BTile<64>::SMEM + NORMIN_BYTES, st>>>(a);
-        else conv_halo3_f6_kernel<128, true><<<a.nblk, NT, BTile<128>::SMEM + NORMIN_BYTES, st>>>(a);
+        if (n64) {
+            HOIG_ROUTE_F(f6_64_normin);
+            conv_halo3_f6_kernel<64, true><<<a.nblk, NT, BTile<64>::SMEM + NORMIN_BYTES, st>>>(a);
+        } else {
+            HOIG_ROUTE_F(f6_128_normin);
+            conv_halo3_f6_kernel<128, true><<<a.nblk, NT, BTile<128>::SMEM + NORMIN_BYTES, st>>>(a);
+        }
         HOIG_LAUNCH_CHECK();
         return HOIG_OK;
     }
-    if (n64) conv_halo3_f6_kernel<64><<<a.nblk, NT, BTile<64>::SMEM, st>>>(a);
-    else conv_halo3_f6_kernel<128><<<a.nblk, NT, BTile<128>::SMEM, st>>>(a);
+    if (n64) {
+        HOIG_ROUTE_F(f6_64);
+        conv_halo3_f6_kernel<64><<<a.nblk, NT, BTile<64>::SMEM, st>>>(a);
+    } else {
+        HOIG_ROUTE_F(f6_128);
+        conv_halo3_f6_kernel<128><<<a.nblk, NT, BTile<128>::SMEM, st>>>(a);
+    }
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

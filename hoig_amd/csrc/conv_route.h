@@ -40,7 +40,9 @@
     FD(igemm_bf16_128x128) FD(igemm_bf16_128x128w) FD(igemm_bf16_64x128) FD(igemm_bf16_128x64) FD(igemm_bf16_64x64)                \
     /* dgrad_k128.hip, conv_thin.hip, conv_small.hip */                                                                            \
     D(k128) D(thin) D(thin_out) D(small)                                                                                           \
-    F(head7) F(small) F(small_ci) F(dot) F(thin) F(thin_out)
+    F(head7) F(small) F(small_ci) F(dot) F(thin) F(thin_out)                                                                       \
+    /* conv_f6.hip: launch_f6 (64- / 128-channel tiles; _normin: norm folded into the loader) */                                    \
+    F(f6_64) F(f6_128) F(f6_64_normin) F(f6_128_normin)
 
 enum HoigConvRoute {
     HOIG_ROUTE_NONE = 0,

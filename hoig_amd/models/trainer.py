@@ -572,6 +572,7 @@ class Trainer(BaseModel):
                     torch.cuda.current_stream().wait_stream(self._side)
             graph, _ = self._capture(body)
             st['graphs'] = (graph,)
+            st['packs'] = [o.captured_packs() for o in opts]      # (what a replay leaves current: FusedAdam.replayed)
             # the capture ran the host side of one step without executing it: the replay that follows does
             for o, b in zip(opts, before):
                 o.step_count = b
@@ -593,9 +594,9 @@ class Trainer(BaseModel):
             if trainable:
                 self._optimizer_D.sync_state()
             st['graphs'][0].replay()
-            self._optimizer_G.replayed()
+            self._optimizer_G.replayed(*st['packs'][0])
             if trainable:
-                self._optimizer_D.replayed()
+                self._optimizer_D.replayed(*st['packs'][1])
             return
         g1, g2 = st['graphs']
         self._wait_g()

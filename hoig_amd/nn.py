@@ -458,11 +458,28 @@ class FusedAdam(object):
             self._state.copy_(torch.tensor(want, dtype=torch.float64))
             self._on_device = want
 
-    def replayed(self):
-        """A captured step of this optimiser has been replayed: the device advanced its step count, follow it."""
+    def captured_packs(self):
+        """Right after a step of this optimiser was CAPTURED: (did the capture re-pack the operand planes?, the fp6 records?).  The
+        step bumped the version inside the capture, so whatever is current now was packed by a launch the graph holds: the planes in a
+        16-bit arithmetic or wherever their buffers existed, the records in the f16f6 arithmetic.  Nothing in an f32 capture of a tree
+        that has never made planes."""
+        t = self.tree
+        return (bool(t._plane_bufs) and t._plane_version == t.version,
+                t._f6 is not None and t._f6['bufs'] is not None and t._f6['version'] == t.version)
+
+    def replayed(self, planes=False, records=False):
+        """A captured step of this optimiser has been replayed: the device advanced its step count and moved the weights, follow it.
+        planes / records: captured_packs() of the replayed graph -- what the graph re-packed itself stays current, everything else
+        that is cached per weight version (planes or fp6 records an eval forward made between two replays, ops._plane_cache) is
+        stale from here on and re-made by whoever asks next."""
         self.step_count += 1
         self._on_device = self._on_device[:4] + (float(self.step_count),)
-        # (tree.version stays: it only keys the operand-plane caches, which the captured step re-packs itself)
+        tree = self.tree
+        tree.version += 1
+        if planes:
+            tree._plane_version = tree.version
+        if records and tree._f6 is not None:
+            tree._f6['version'] = tree.version
 
     def step(self, grad_scale=1.0, ready=None):
         """One Adam step over the flat buffers.  `ready` (DDP): an iterator of (begin, end) element ranges whose gradients

@@ -139,17 +139,17 @@ def _relerr(a, ref):
     return ((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
 
 
-def rounded_operand_error(case, mode):
+def rounded_operand_error(case, mode, passes=('y', 'dx', 'dw')):
     """{'y', 'dx', 'dw'} -> the max-norm relative error that `mode`'s operand rounding alone leaves in each pass of `case` (a Case, or
     the (x, w, b, gy, stride, pad, transposed) operands themselves), against the unrounded float64 reference.  Exact accumulation:
-    this is the arithmetic's own error, computed from the reference alone -- a kernel's error is compared WITH it, never used for it."""
+    this is the arithmetic's own error, computed from the reference alone -- a kernel's error is compared WITH it, never used for it.
+    passes=('y',): the forward alone (the gradients' float64 references are the expensive part; gy may then be None)."""
     if isinstance(case, Case):
         x, w, b, gy = make_case(case)
         stride, pad, transposed = case.stride, case.pad, case.transposed
     else:
         x, w, b, gy, stride, pad, transposed = case
     y0 = conv_ref(x, w, None, stride, pad, transposed)
-    dx0, dw0, _ = conv_grads_ref(x, w, None, gy, stride, pad, transposed)
     hw = tuple(y0.shape[1:3])
     out = {}
     # forward: x gathered, w the other operand; fp16 terms, weight planes hold fp16(2^8 w)
@@ -159,6 +159,9 @@ def rounded_operand_error(case, mode):
     if ng == 2 and no == 2:
         y = y - conv_ref(xl, wl, None, stride, pad, transposed, hw=hw)
     out['y'] = _relerr(y, y0)
+    if 'dx' not in passes and 'dw' not in passes:          # (a forward-only caller: gy may be None)
+        return out
+    dx0, dw0, _ = conv_grads_ref(x, w, None, gy, stride, pad, transposed)
     # data gradient: dy gathered, w the other operand; bf16 terms
     ng, no = _PASS_MODE[_mode_of_pass(mode, 'dx')]
     (gh, gl), (wh, wl) = _terms(gy, ng, torch.bfloat16), _terms(w, no, torch.bfloat16)
