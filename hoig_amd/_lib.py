@@ -19,6 +19,7 @@ PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16X2, PREC_F16F6 = 0, 1, 2, 3, 4
 LOSS_L1, LOSS_MSE, LOSS_BCE = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 JPEG_SUBSEQ_BYTES = 64              # HOIG_JPEG_SUBSEQ_BYTES
+PNG_SEGMENT_BYTES = 8192            # HOIG_PNG_SEGMENT_BYTES
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
 
 
@@ -164,6 +165,10 @@ _SIGS = {
     'hoig_pil_bilinear_table': [_i, _i, _vp],
     'hoig_resize_pil_bilinear_u8_host': [_vp, _i, _i, _i, _i, _vp, _i, _i],
     'hoig_resize_pil_bilinear_u8': [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    'hoig_png_encode_u8': [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp],
+    'hoig_png_filter_host': [_vp, _i, _i, _i, _vp],
+    'hoig_png_deflate_host': [_vp, _i64, _i, _i, _i, _vp, _i64, ctypes.POINTER(ctypes.c_int64), _vp],
+    'hoig_png_encode_host': [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _i],
 }
 
 
@@ -201,6 +206,10 @@ def _load():
     lib.hoig_ssim_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_resize_pil_bilinear_u8_workspace_bytes.argtypes = [_i] * 6
     lib.hoig_resize_pil_bilinear_u8_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_png_encode_bound.argtypes = [_i] * 4
+    lib.hoig_png_encode_bound.restype = ctypes.c_int64
+    lib.hoig_png_encode_workspace_bytes.argtypes = [_i] * 5
+    lib.hoig_png_encode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]

@@ -11,6 +11,10 @@ and crop (r, c) = (i // cols, i % cols) with cols = grid_width // side.  The gri
 denormalise + tile kernel (``hoig_tensor2im_u8``), one device-to-host copy per grid; encoding and file writes run on a small
 thread pool so that the next batch's forward is not held up by zlib (the reference writes synchronously).  ``write_images`` writes the
 same files from the per-sample device bytes of ``Trainer.eval_images_u8`` (no visuals, no grid).
+
+``EvalWriter(..., device_png=True)`` (or ``HOIG_DEVICE_PNG=1``; off by default) lets ``write_images`` encode the sets that arrive as
+device tensors on the device (hoig_amd.png, docs/png_encode.md): the compressed files cross to the host instead of the raw pixels and
+the pool only writes them.  The files decode to the same pixels; their bytes are not Pillow's.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -43,11 +47,17 @@ def _save_png(arr, path):
     Image.fromarray(np.ascontiguousarray(arr)).save(path)
 
 
+def _save_bytes(data, path):
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
 class EvalWriter(object):
     """``w = EvalWriter(out_dir, sav_gt=True); w.write(model.get_current_visuals(), batch['nameA'], batch['nameB']); w.close()``"""
 
-    def __init__(self, out_dir, sav_gt=True, side=256, workers=4):
+    def __init__(self, out_dir, sav_gt=True, side=256, workers=4, device_png=None):
         self.out_dir, self.side = out_dir, side
+        self.device_png = os.environ.get('HOIG_DEVICE_PNG', '') == '1' if device_png is None else bool(device_png)
         self.grids = [g for g in GRIDS if sav_gt or g[0] != 'gt']
         for sub, _ in self.grids:                                  # eval.py:47-53
             os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
@@ -64,16 +74,33 @@ class EvalWriter(object):
 
     def write_images(self, images_u8, names_a, names_b):
         """The files of write() from Trainer.eval_images_u8's dict (uint8 [B,H,W,3] per set, on the device or the host): one
-        device-to-host copy per set, no grid to crop.  Scoring in memory (hoig_amd.metrics.stream) and keeping the PNGs share a loop."""
+        device-to-host copy per set, no grid to crop.  Scoring in memory (hoig_amd.metrics.stream) and keeping the PNGs share a loop.
+        With device_png, a set that is a device tensor is encoded there and the copy carries the finished files."""
         if len(names_a) != len(names_b):
             raise ValueError('nameA / nameB length mismatch')
         for sub, _ in self.grids:
             batch = images_u8[sub]
+            if self.device_png and getattr(batch, 'is_cuda', False):
+                self._write_device(sub, batch, names_a, names_b)
+                continue
             batch = batch.cpu().numpy() if hasattr(batch, 'cpu') else np.asarray(batch)
             if batch.ndim != 4 or batch.dtype != np.uint8 or batch.shape[0] < len(names_a):
                 raise ValueError('%s: uint8 [B,H,W,C] with B >= %d expected, got %s %s' % (sub, len(names_a), batch.dtype, batch.shape))
             for crop, a, b in zip(batch, names_a, names_b):
                 self._save(crop, os.path.join(self.out_dir, sub, pair_name(a, b)), owned=True)
+
+    def _write_device(self, sub, batch, names_a, names_b):
+        import torch
+        from . import png
+        if batch.dim() != 4 or batch.dtype != torch.uint8 or batch.shape[0] < len(names_a):
+            raise ValueError('%s: uint8 [B,H,W,C] with B >= %d expected, got %s %s' % (sub, len(names_a), batch.dtype, tuple(batch.shape)))
+        for data, a, b in zip(png.encode_u8(batch[:len(names_a)]), names_a, names_b):
+            path = os.path.join(self.out_dir, sub, pair_name(a, b))
+            if self._pool is None:
+                _save_bytes(data, path)
+            else:
+                self._pending.append(self._pool.submit(_save_bytes, data, path))
+            self.written += 1
 
     def _save(self, crop, path, owned=False):
         if self._pool is None:

@@ -736,6 +736,35 @@ int hoig_jpeg_decode_bgr_u8_par(const uint8_t *bytes, int64_t nbytes, const hoig
                                 int n, const int32_t *intervals, int64_t n_entries, uint8_t *out, int64_t out_bytes, int32_t *status,
                                 void *workspace, int64_t workspace_bytes, int subseq_bytes, hoig_stream_t stream);
 
+/* ---- PNG FILES ENCODED ON THE DEVICE (hoig_amd/csrc/png.hip, png_deflate.h, png_host.cpp; docs/png_encode.md): uint8 [B][H][W][C],
+ *      C = 3 or 1, to B ordinary PNG files (8 bit, colour type 2 or 0, no interlace, no ancillary chunk) that decode to the input.
+ *      Each row takes the filter with the smallest sum of absolute (signed) values; the filtered stream of H (1 + W C) bytes is cut
+ *      into segments of `segment_bytes`, each a deflate block of its own (dynamic Huffman, or stored where that is not larger) closed
+ *      by an empty stored block and carried by an IDAT chunk of its own; the Adler-32 follows in a 4-byte IDAT.  The bytes are a
+ *      function of the input and segment_bytes alone.  segment_bytes: 0 (HOIG_PNG_SEGMENT_BYTES), 4096, 8192, 16384 or 32768;
+ *      anything else is HOIG_EINVAL.  C outside {1, 3}, a size < 1 or a filtered stream of 2^31 bytes or more: HOIG_EUNSUPPORTED. ---- */
+#define HOIG_PNG_SEGMENT_BYTES 8192
+/* HOST, no HIP call: the bytes to reserve per image in `out` (negative: the code above) and the device workspace of a batch */
+int64_t hoig_png_encode_bound(int H, int W, int C, int segment_bytes);
+int64_t hoig_png_encode_workspace_bytes(int B, int H, int W, int C, int segment_bytes);
+/* src, out, sizes [B], workspace (16-byte aligned) in device memory: image i's file is out[i * out_stride .. + sizes[i]), the rest of
+ * its slot is left alone.  out_stride >= hoig_png_encode_bound, workspace_bytes >= hoig_png_encode_workspace_bytes (HOIG_EINVAL
+ * otherwise, before any launch).  Three launches on `stream`; never synchronises, allocates nothing. */
+int hoig_png_encode_u8(const uint8_t *src, int B, int H, int W, int C, uint8_t *out, int64_t out_stride, int32_t *sizes, void *workspace,
+                       int64_t workspace_bytes, int segment_bytes, hoig_stream_t stream);
+/* HOST twins (the same per-lane code, a workgroup walked lane by lane and phase by phase; no HIP call, host memory).
+ * hoig_png_filter_host: one image [H][W][C] -> its filtered stream, H (1 + W C) bytes.
+ * hoig_png_deflate_host: any byte stream -> the zlib stream (header, the segments, Adler-32) in out[0 .. *out_size); out_bytes >=
+ *   2 + n + 10 * segments + 4.  dist_c / dist_row: the two fixed match distances tried next to 1 and the hash table's (0: none);
+ *   dist_c = -1: no match search, every byte a literal (crafted streams reach the Huffman edge cases with it).
+ *   seg_sizes (optional) [segments]: the bytes of each segment's blocks.
+ * hoig_png_encode_host: what hoig_png_encode_u8 writes, byte for byte. */
+int hoig_png_filter_host(const uint8_t *src, int H, int W, int C, uint8_t *filtered);
+int hoig_png_deflate_host(const uint8_t *stream, int64_t n, int segment_bytes, int dist_c, int dist_row, uint8_t *out, int64_t out_bytes,
+                          int64_t *out_size, int32_t *seg_sizes);
+int hoig_png_encode_host(const uint8_t *src, int B, int H, int W, int C, uint8_t *out, int64_t out_stride, int32_t *sizes,
+                         int segment_bytes);
+
 #ifdef __cplusplus
 }
 #endif
