@@ -20,6 +20,8 @@ LOSS_L1, LOSS_MSE, LOSS_BCE = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 JPEG_SUBSEQ_BYTES = 64              # HOIG_JPEG_SUBSEQ_BYTES
 PNG_SEGMENT_BYTES = 8192            # HOIG_PNG_SEGMENT_BYTES
+# HOIG_PNG_E*: the bits of a PNG decoder status word
+PNG_ECODE, PNG_EBTYPE, PNG_ESTORED, PNG_EDIST, PNG_EEARLY, PNG_EMORE, PNG_ELESS, PNG_EFILTER, PNG_EADLER = 1, 2, 4, 8, 16, 32, 64, 128, 256
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
 
 
@@ -169,6 +171,9 @@ _SIGS = {
     'hoig_png_filter_host': [_vp, _i, _i, _i, _vp],
     'hoig_png_deflate_host': [_vp, _i64, _i, _i, _i, _vp, _i64, ctypes.POINTER(ctypes.c_int64), _vp],
     'hoig_png_encode_host': [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _i],
+    'hoig_png_inflate_host': [_vp, _i64, _vp, _i64, _vp],
+    'hoig_png_decode_host': [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _i64, _i],
+    'hoig_png_decode_u8': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp],
 }
 
 
@@ -210,6 +215,8 @@ def _load():
     lib.hoig_png_encode_bound.restype = ctypes.c_int64
     lib.hoig_png_encode_workspace_bytes.argtypes = [_i] * 5
     lib.hoig_png_encode_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_png_decode_workspace_bytes.argtypes = [_vp, _i]
+    lib.hoig_png_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]

@@ -26,6 +26,9 @@ Entry g_table[HOIG_TUNE_COUNT] = {
     // halo kernel of conv_halo5.hip, forward and data gradient; 0: the generic implicit GEMM, as before that kernel existed;
     // 2: as 1, without its split over K on launches of few tiles
     {"halo5", 1},
+    // the PNG decoder's inflate window (png_decode.hip): 0 a 32 KiB ring in LDS; 1 the image's own filtered stream in the workspace, a
+    // workgroup-scope fence between a store and a later read of it (the A/B of profiles/png_decode.txt)
+    {"png_window", 0},
 };
 }  // namespace
 

@@ -20,6 +20,9 @@ def parser():
     p.add_argument('--precision', default=None, help="convolution arithmetic: 'bf16x3' (default) or 'f32'")
     p.add_argument('--device-resize', action='store_true',
                    help='lpips / ssim: run the two PIL resizes of get_eval_loader on the device (the same bytes; workers only decode)')
+    p.add_argument('--device-png-decode', action='store_true', default=None,
+                   help='decode the PNG files the device decoder supports on the device (the same bytes; the workers only read the '
+                        'files); lpips / ssim: implies --device-resize.  HOIG_DEVICE_PNG_DECODE=1 does the same')
     return p
 
 
@@ -32,16 +35,18 @@ def main(argv=None):
             raise RuntimeError('Invalid path: %s' % p)
     if a.metric == 'fid':
         from .fid import calculate_fid_given_paths
-        v = calculate_fid_given_paths(a.path, a.batch_size or 50, a.device, a.dims, a.inception_weights, a.precision)
+        v = calculate_fid_given_paths(a.path, a.batch_size or 50, a.device, a.dims, a.inception_weights, a.precision,
+                                      device_png_decode=a.device_png_decode)
         print('FID: ', v)
     elif a.metric == 'lpips':
         from .lpips import calculate_lpips_given_paths
         v = calculate_lpips_given_paths(a.path, a.img_size, a.batch_size or 50, a.alexnet_weights, a.lpips_weights, a.precision,
-                                        a.device, device_resize=a.device_resize)
+                                        a.device, device_resize=a.device_resize, device_png_decode=a.device_png_decode)
         print('LPIPS: ', v)
     else:
         from .ssim import calculate_ssim_given_paths
-        v = calculate_ssim_given_paths(a.path, a.img_size, a.batch_size or 1, a.device, device_resize=a.device_resize)
+        v = calculate_ssim_given_paths(a.path, a.img_size, a.batch_size or 1, a.device, device_resize=a.device_resize,
+                                       device_png_decode=a.device_png_decode)
         print('SSIM: ', v[0], ' MS-SSIM: ', v[1])
     return v
 

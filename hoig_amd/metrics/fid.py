@@ -169,23 +169,25 @@ def _model(model, dims, device, weights, precision):
     return model
 
 
-def get_activations(files, model, batch_size=50, dims=2048, device=None, weights=None, precision=None):
-    """fid_score.py get_activations: (len(files), dims) fp64 activations, batch_size clipped to the number of files."""
+def get_activations(files, model, batch_size=50, dims=2048, device=None, weights=None, precision=None, device_png_decode=None):
+    """fid_score.py get_activations: (len(files), dims) fp64 activations, batch_size clipped to the number of files.
+    device_png_decode (HOIG_DEVICE_PNG_DECODE=1): the supported PNG files are decoded on the device (images.DeviceBatches)."""
     model = _model(model, dims, device, weights, precision)
     if batch_size > len(files):
         print('Warning: batch size is bigger than the data size. Setting batch size to data size')
         batch_size = len(files)
     pred = np.empty((len(files), dims))
     start = 0
-    for u8 in I.DeviceBatches(I.batches_of(list(files), batch_size), model.device):
+    for u8 in I.DeviceBatches(I.batches_of(list(files), batch_size), model.device, device_png_decode=device_png_decode):
         f = model.features_u8(u8).double().cpu().numpy()
         pred[start:start + f.shape[0]] = f
         start += f.shape[0]
     return pred
 
 
-def calculate_activation_statistics(files, model, batch_size=50, dims=2048, device=None, weights=None, precision=None):
-    act = get_activations(files, model, batch_size, dims, device, weights, precision)
+def calculate_activation_statistics(files, model, batch_size=50, dims=2048, device=None, weights=None, precision=None,
+                                    device_png_decode=None):
+    act = get_activations(files, model, batch_size, dims, device, weights, precision, device_png_decode)
     return np.mean(act, axis=0), np.cov(act, rowvar=False)
 
 
@@ -209,18 +211,18 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
     return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
 
 
-def compute_statistics_of_path(path, model, batch_size, dims, device=None, weights=None, precision=None):
+def compute_statistics_of_path(path, model, batch_size, dims, device=None, weights=None, precision=None, device_png_decode=None):
     if str(path).endswith('.npz'):
         with np.load(path) as f:
             return f['mu'][:], f['sigma'][:]
-    return calculate_activation_statistics(I.list_images(path), model, batch_size, dims, device, weights, precision)
+    return calculate_activation_statistics(I.list_images(path), model, batch_size, dims, device, weights, precision, device_png_decode)
 
 
-def calculate_fid_given_paths(paths, batch_size, device, dims, weights=None, precision=None):
+def calculate_fid_given_paths(paths, batch_size, device, dims, weights=None, precision=None, device_png_decode=None):
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError('Invalid path: %s' % p)
     model = InceptionFeatures(weights, dims, precision, device)
-    m1, s1 = compute_statistics_of_path(paths[0], model, batch_size, dims, device)
-    m2, s2 = compute_statistics_of_path(paths[1], model, batch_size, dims, device)
+    m1, s1 = compute_statistics_of_path(paths[0], model, batch_size, dims, device, device_png_decode=device_png_decode)
+    m2, s2 = compute_statistics_of_path(paths[1], model, batch_size, dims, device, device_png_decode=device_png_decode)
     return calculate_frechet_distance(m1, s1, m2, s2)

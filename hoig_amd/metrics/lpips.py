@@ -99,15 +99,19 @@ def calculate_lpips_given_images(gen_images, gt_images, alexnet_weights=None, lp
 
 
 def calculate_lpips_given_paths(paths, img_size=256, batch_size=50, alexnet_weights=None, lpips_weights=None, precision=None,
-                                device=None, model=None, device_resize=False):
+                                device=None, model=None, device_resize=False, device_png_decode=None):
     """LPIPS between two directories of images (sorted, paired by position), in get_eval_loader's preprocessing (PIL resize to
     img_size, then to 299, ImageNet normalisation).  As in lpips.py, the result is the MEAN OF PER-BATCH MEANS: a short last batch
     counts as much as a full one (7 images in batches of 3 weigh the 7th image three times as much as each of the others).
     device_resize: the workers only decode and the two PIL resizes run on the device (kernels.pil_resize_chain_u8: the same bytes,
-    so the same value)."""
+    so the same value).  device_png_decode (HOIG_DEVICE_PNG_DECODE=1): the supported PNG files are decoded on the device too
+    (images.DeviceBatches); it implies device_resize."""
+    device_png_decode = I.png_decode_option(device_png_decode)
+    device_resize = device_resize or device_png_decode
     print('Calculating LPIPS given paths %s and %s...' % (paths[0], paths[1]))
     model = model or LPIPS(alexnet_weights, lpips_weights, precision, device)
-    batches = I.DeviceBatches(paired_batches(paths, batch_size), model.device, None if device_resize else img_size)
+    batches = I.DeviceBatches(paired_batches(paths, batch_size), model.device, None if device_resize else img_size,
+                              device_png_decode=device_png_decode)
     if device_resize:
         batches = (K.pil_resize_chain_u8(u8, img_size) for u8 in batches)
     means = [model.distance_u8(u8).mean() for u8 in batches]

@@ -95,17 +95,21 @@ def ssim_pairs_u8(u8):
     return ssim_nhwc(xy, 255).mean(1), ms_ssim_nhwc(xy, 255).mean(1)
 
 
-def calculate_ssim_given_paths(paths, img_size=256, batch_size=1, device=None, device_resize=False):
+def calculate_ssim_given_paths(paths, img_size=256, batch_size=1, device=None, device_resize=False, device_png_decode=None):
     """(SSIM, MS-SSIM) means over two directories of images paired by sorted position, with the reference's inputs exactly
     (metrics/ssim.py): get_eval_loader's transform (PIL resize to img_size, then to 299 x 299, ImageNet Normalize) and
     data_range=255 on those normalised tensors.  Their range is about 5, not 255, so C1 and C2 dominate and both values sit close to
     1: that is the reference's setting, reproduced, not corrected.  device_resize: the workers only decode and the two PIL resizes run
-    on the device (kernels.pil_resize_chain_u8: the same bytes, so the same values)."""
+    on the device (kernels.pil_resize_chain_u8: the same bytes, so the same values).  device_png_decode (HOIG_DEVICE_PNG_DECODE=1): the
+    supported PNG files are decoded on the device too (images.DeviceBatches); it implies device_resize."""
     from .lpips import paired_batches
+    device_png_decode = I.png_decode_option(device_png_decode)
+    device_resize = device_resize or device_png_decode
     print('Calculating SSIM given paths %s and %s...' % (paths[0], paths[1]))
     dev = torch.device(device if device is not None else 'cuda')
     s_all, m_all = [], []
-    for u8 in I.DeviceBatches(paired_batches(paths, batch_size), dev, None if device_resize else img_size):
+    for u8 in I.DeviceBatches(paired_batches(paths, batch_size), dev, None if device_resize else img_size,
+                              device_png_decode=device_png_decode):
         s, m = ssim_pairs_u8(KR.pil_resize_chain_u8(u8, img_size) if device_resize else u8)
         s_all.append(s)
         m_all.append(m)

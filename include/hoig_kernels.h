@@ -585,6 +585,9 @@ const char *hoig_version(void);
  *                kernel covers (<= 256 workgroups: 8 images of 512 -> 512 at 32 x 32) go to hoig_conv2d_fwd_wino.  Alone such a launch
  *                is 37 % faster; in the step they are the src / tsf twins, which already share the chip
  *                (profiles/r06_winograd_ab.txt: the in-step A/B); off
+ *   "png_window" 0  the window of the PNG decoder's inflate kernel (hoig_png_decode_u8): 0 a 32 KiB ring in LDS, barriers that order LDS
+ *                only; 1 the image's own filtered stream in the workspace with a workgroup-scope fence between a store and a later read
+ *                of it.  The same bytes; profiles/png_decode.txt has the A/B
  * Round 6 removed the keys whose losing side had lost two rounds running, and with them that side's code: "wgrad16" (the 3x3 weight
  * gradient on 16x16x32: 5-20 % slower, wgrad_halo16.hip deleted), "mfma16" (the 8-row 3x3 stride-1 tilings on 16x16x32: always; their
  * 32x32x16 instantiations are gone), "wgrad_ko" (knock-out instantiations of the LDS-DMA weight gradient:
@@ -764,6 +767,53 @@ int hoig_png_deflate_host(const uint8_t *stream, int64_t n, int segment_bytes, i
                           int64_t *out_size, int32_t *seg_sizes);
 int hoig_png_encode_host(const uint8_t *src, int B, int H, int W, int C, uint8_t *out, int64_t out_stride, int32_t *sizes,
                          int segment_bytes);
+
+/* ---- PNG FILES DECODED ON THE DEVICE (hoig_amd/csrc/png_decode.hip, png_inflate.h, png_decode_host.cpp; hoig_amd/png_decode.py walks
+ *      the chunks on the host; docs/png_decode.md).  Non-interlaced files of colour type 0, 2, 3, 4, 6 at 8 bits and of type 0 and 3 at
+ *      1, 2 and 4 bits, without tRNS.  The result is np.asarray(Image.open(f).convert('RGB')), byte for byte: uint8 [H][W][3] (grey
+ *      scaled to 0..255, palette entries looked up, alpha dropped), or the same in B, G, R order.
+ *      Two launches per batch: inflate (one 64-lane workgroup per image: stored, fixed and dynamic blocks, tables and a 32 KiB window
+ *      in LDS, the Adler-32 compared at the end) -> the filtered stream in the workspace; unfilter + convert (a workgroup per image,
+ *      rows as a skewed pipeline) -> RGB / BGR. ---- */
+enum { HOIG_PNG_ECODE = 1,      /* no code matches, a code is over-subscribed or incomplete, or the block header's counts are invalid */
+       HOIG_PNG_EBTYPE = 2,     /* block type 3 */
+       HOIG_PNG_ESTORED = 4,    /* a stored block's LEN and NLEN disagree */
+       HOIG_PNG_EDIST = 8,      /* a match reaches in front of the stream */
+       HOIG_PNG_EEARLY = 16,    /* the data ends inside a block, or before the Adler-32 */
+       HOIG_PNG_EMORE = 32,     /* more output than height * (1 + row bytes) */
+       HOIG_PNG_ELESS = 64,     /* less output than that */
+       HOIG_PNG_EFILTER = 128,  /* a row's filter type is above 4 */
+       HOIG_PNG_EADLER = 256    /* the Adler-32 of the filtered stream is not the stored one */ };
+/* One image of a batch.  The caller fills everything above `filt_off`; hoig_png_decode_workspace_bytes fills that. */
+typedef struct hoig_png_decode_plan {
+    int64_t data_off;          /* first byte of the zlib stream (the IDAT payloads, concatenated) in the packed buffer; % 16 == 0 */
+    int64_t out_off;           /* first byte of this image's [height][width][3] result in the output buffer */
+    int64_t pal_off;           /* first byte of the PLTE payload in the packed buffer (colour type 3; otherwise unused) */
+    int64_t filt_off;          /* workspace: the filtered stream, height * (1 + row bytes) */
+    int32_t data_len;          /* bytes of the zlib stream, header and Adler-32 included */
+    int32_t width, height;
+    int32_t color_type;        /* 0, 2, 3, 4, 6 */
+    int32_t bit_depth;         /* 8; 1, 2, 4 as well for colour types 0 and 3 */
+    int32_t pal_entries;       /* PLTE entries (colour type 3: 1 .. 256; an index at or above it is black, as in Pillow) */
+    int32_t reserved[2];
+} hoig_png_decode_plan;
+/* HOST, no HIP call: checks the n plans, writes each one's filt_off and returns the workspace size in bytes (< 0: a plan is outside
+ * the supported set, or its filtered stream has 2^31 bytes or more) */
+int64_t hoig_png_decode_workspace_bytes(hoig_png_decode_plan *plans, int n);
+/* HOST twin of the inflate kernel alone (the same per-lane code, the workgroup walked lane by lane; no HIP call): the zlib stream
+ * data[0 .. data_len) -> out[0 .. expect) and *status (0 or HOIG_PNG_E* bits; `expect` is the size the stream must have).  data must
+ * be readable up to data_len rounded up to 16.  A bad STREAM is a status, not a return code. */
+int hoig_png_inflate_host(const uint8_t *data, int64_t data_len, uint8_t *out, int64_t expect, int32_t *status);
+/* HOST twin of the whole call: what hoig_png_decode_u8 writes to out and status, byte for byte; all pointers host memory. */
+int hoig_png_decode_host(const uint8_t *bytes, int64_t nbytes, const hoig_png_decode_plan *plans, int n, uint8_t *out,
+                         int64_t out_bytes, int32_t *status, void *workspace, int64_t workspace_bytes, int bgr);
+/* The batch on the device.  bytes (nbytes % 16 == 0, 16-byte aligned), plans_dev, out, status, workspace (16-byte aligned): device
+ * memory; plans_host: the same plans in host memory, read at the call (sizes and offsets are checked there: HOIG_EINVAL before any
+ * launch).  Images may differ in size and kind.  status[i] is written by the device; an image with a status leaves its slot of `out`
+ * unspecified, and nothing outside the slots and the workspace is written.  Never synchronises, allocates nothing. */
+int hoig_png_decode_u8(const uint8_t *bytes, int64_t nbytes, const hoig_png_decode_plan *plans_host,
+                       const hoig_png_decode_plan *plans_dev, int n, uint8_t *out, int64_t out_bytes, int32_t *status, void *workspace,
+                       int64_t workspace_bytes, int bgr, hoig_stream_t stream);
 
 #ifdef __cplusplus
 }
