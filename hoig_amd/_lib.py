@@ -20,6 +20,7 @@ LOSS_L1, LOSS_MSE, LOSS_BCE = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 JPEG_SUBSEQ_BYTES = 64              # HOIG_JPEG_SUBSEQ_BYTES
 PNG_SEGMENT_BYTES = 8192            # HOIG_PNG_SEGMENT_BYTES
+GEMM_ACCUMULATE, GEMM_SYMMETRIC, GEMM_F32 = 1, 2, 4      # HOIG_GEMM_*
 # HOIG_PNG_E*: the bits of a PNG decoder status word
 PNG_ECODE, PNG_EBTYPE, PNG_ESTORED, PNG_EDIST, PNG_EEARLY, PNG_EMORE, PNG_ELESS, PNG_EFILTER, PNG_EADLER = 1, 2, 4, 8, 16, 32, 64, 128, 256
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
@@ -174,6 +175,15 @@ _SIGS = {
     'hoig_png_inflate_host': [_vp, _i64, _vp, _i64, _vp],
     'hoig_png_decode_host': [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _i64, _i],
     'hoig_png_decode_u8': [_vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp],
+    'hoig_gemm_tn_f64': [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _vp],
+    'hoig_gemm_tn_f64_host': [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i],
+    'hoig_pchol_f64': [_vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp],
+    'hoig_pchol_f64_host': [_vp, _i64, _i, _vp, _i64, _vp, _vp],
+    'hoig_sym_eigvals_f64': [_vp, _i64, _i, _vp, _vp, _vp, _i64, _vp],
+    'hoig_sym_eigvals_f64_host': [_vp, _i64, _i, _vp, _vp],
+    'hoig_tridiag_eigvals_f64': [_vp, _vp, _i, _vp, _vp],
+    'hoig_tridiag_eigvals_f64_host': [_vp, _vp, _i, _vp],
+    'hoig_sym_tridiag_f64_host': [_vp, _i64, _i, _vp, _vp],
 }
 
 
@@ -217,6 +227,10 @@ def _load():
     lib.hoig_png_encode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_png_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_png_decode_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_pchol_f64_workspace_bytes.argtypes = [_i]
+    lib.hoig_pchol_f64_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_sym_eigvals_f64_workspace_bytes.argtypes = [_i]
+    lib.hoig_sym_eigvals_f64_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]

@@ -23,6 +23,9 @@ def parser():
     p.add_argument('--device-png-decode', action='store_true', default=None,
                    help='decode the PNG files the device decoder supports on the device (the same bytes; the workers only read the '
                         'files); lpips / ssim: implies --device-resize.  HOIG_DEVICE_PNG_DECODE=1 does the same')
+    p.add_argument('--device-fid', action='store_true', default=None,
+                   help='fid: streaming fp64 moments and the Frechet distance on the device instead of np.cov and scipy sqrtm (close '
+                        'to the default value, not equal: docs/fid_device.md).  HOIG_DEVICE_FID=1 does the same')
     return p
 
 
@@ -36,7 +39,7 @@ def main(argv=None):
     if a.metric == 'fid':
         from .fid import calculate_fid_given_paths
         v = calculate_fid_given_paths(a.path, a.batch_size or 50, a.device, a.dims, a.inception_weights, a.precision,
-                                      device_png_decode=a.device_png_decode)
+                                      device_png_decode=a.device_png_decode, device_stats=a.device_fid)
         print('FID: ', v)
     elif a.metric == 'lpips':
         from .lpips import calculate_lpips_given_paths

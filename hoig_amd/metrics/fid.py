@@ -3,7 +3,8 @@ the reference's names and signatures (weight arguments added at the end).
 
 Convolutions run on hoig_conv2d_fwd with BatchNorm (eps 1e-3) folded into their weights and biases at load time, ReLU in the
 epilogue; the default arithmetic is the three-term 16-bit forward (``precision='bf16x3'``, about fp32-accurate), ``precision='f32'``
-gives exact fp32 products.  Statistics, the covariance and sqrtm stay on the host in fp64, as in the reference.
+gives exact fp32 products.  Statistics, the covariance and sqrtm stay on the host in fp64, as in the reference; ``device_stats=True``
+(HOIG_DEVICE_FID=1, off by default) keeps them on the device instead (fid_device.py, docs/fid_device.md).
 """
 import os
 
@@ -186,7 +187,20 @@ def get_activations(files, model, batch_size=50, dims=2048, device=None, weights
 
 
 def calculate_activation_statistics(files, model, batch_size=50, dims=2048, device=None, weights=None, precision=None,
-                                    device_png_decode=None):
+                                    device_png_decode=None, device_stats=None):
+    """device_stats (HOIG_DEVICE_FID=1): the same batches go into streaming fp64 moments on the device (fid_device.Moments) and only
+    mu and sigma come back; close to the default's values, not equal."""
+    from .fid_device import Moments, fid_device_option
+    if fid_device_option(device_stats):
+        model = _model(model, dims, device, weights, precision)
+        files = list(files)
+        if batch_size > len(files):
+            print('Warning: batch size is bigger than the data size. Setting batch size to data size')
+            batch_size = len(files)
+        moments = Moments(dims, model.device)
+        for u8 in I.DeviceBatches(I.batches_of(files, batch_size), model.device, device_png_decode=device_png_decode):
+            moments.update(model.features_u8(u8))
+        return moments.statistics_host()
     act = get_activations(files, model, batch_size, dims, device, weights, precision, device_png_decode)
     return np.mean(act, axis=0), np.cov(act, rowvar=False)
 
@@ -211,18 +225,27 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
     return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
 
 
-def compute_statistics_of_path(path, model, batch_size, dims, device=None, weights=None, precision=None, device_png_decode=None):
+def compute_statistics_of_path(path, model, batch_size, dims, device=None, weights=None, precision=None, device_png_decode=None,
+                               device_stats=None):
     if str(path).endswith('.npz'):
         with np.load(path) as f:
             return f['mu'][:], f['sigma'][:]
-    return calculate_activation_statistics(I.list_images(path), model, batch_size, dims, device, weights, precision, device_png_decode)
+    return calculate_activation_statistics(I.list_images(path), model, batch_size, dims, device, weights, precision, device_png_decode,
+                                           device_stats)
 
 
-def calculate_fid_given_paths(paths, batch_size, device, dims, weights=None, precision=None, device_png_decode=None):
+def calculate_fid_given_paths(paths, batch_size, device, dims, weights=None, precision=None, device_png_decode=None, device_stats=None):
+    """device_stats (HOIG_DEVICE_FID=1): moments and the distance on the device (fid_device.frechet_distance_device)."""
+    from .fid_device import fid_device_option, frechet_distance_device
+    device_stats = fid_device_option(device_stats)
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError('Invalid path: %s' % p)
     model = InceptionFeatures(weights, dims, precision, device)
-    m1, s1 = compute_statistics_of_path(paths[0], model, batch_size, dims, device, device_png_decode=device_png_decode)
-    m2, s2 = compute_statistics_of_path(paths[1], model, batch_size, dims, device, device_png_decode=device_png_decode)
+    m1, s1 = compute_statistics_of_path(paths[0], model, batch_size, dims, device, device_png_decode=device_png_decode,
+                                        device_stats=device_stats)
+    m2, s2 = compute_statistics_of_path(paths[1], model, batch_size, dims, device, device_png_decode=device_png_decode,
+                                        device_stats=device_stats)
+    if device_stats:
+        return frechet_distance_device(m1, s1, m2, s2, model.device)
     return calculate_frechet_distance(m1, s1, m2, s2)

@@ -14,6 +14,7 @@ import torch
 
 from . import kernels as K
 from .fid import calculate_frechet_distance, compute_statistics_of_path
+from .fid_device import Moments, fid_device_option, frechet_distance_device
 from .ssim import ssim_pairs_u8
 
 
@@ -43,9 +44,14 @@ class Scorer(object):
     'ms_ssim'} (absent metrics omitted), equal to calculate_fid_given_paths([gen, gt], fid_batch, ..), calculate_lpips_given_paths(
     [gen, gt], img_size, lpips_batch, model=lpips) and calculate_ssim_given_paths([gen, gt], img_size, ssim_batch) on directories whose
     sorted file names are in update() order.  FID is between the two streams, or against `fid_reference`: (mu, sigma) or an .npz of
-    them (then the ground truth's features are not taken)."""
+    them (then the ground truth's features are not taken).
 
-    def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None):
+    fid_device (HOIG_DEVICE_FID=1; off by default): the features go into streaming fp64 moments on the device (fid_device.Moments:
+    update() makes no host copy and does not wait for the device) and result() takes the distance with
+    fid_device.frechet_distance_device.  The values are then close to the directory functions', not equal (docs/fid_device.md)."""
+
+    def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None,
+                 fid_device=None):
         self.fid, self.lpips, self.ssim, self.img_size = fid, lpips, bool(ssim), img_size
         self.n = 0
         if isinstance(fid_reference, str):
@@ -53,9 +59,13 @@ class Scorer(object):
                 raise ValueError('fid_reference %r: (mu, sigma) or an .npz of them' % fid_reference)
             fid_reference = compute_statistics_of_path(fid_reference, None, None, None)
         self.fid_reference = fid_reference
+        self.fid_device = False
         if fid is not None:
             self._fid_gen, self._fid_gt = _Batches(fid_batch), (_Batches(fid_batch) if fid_reference is None else None)
             self._feat_gen, self._feat_gt = [], []
+            self.fid_device = fid_device_option(fid_device)
+            if self.fid_device:
+                self._feat_gen, self._feat_gt = Moments(fid.dims, fid.device), Moments(fid.dims, fid.device)
         # the pair metrics that share a batch size share the resized batch
         self._pairs = {}
         if lpips is not None:
@@ -85,7 +95,13 @@ class Scorer(object):
         if gen_u8.shape != gt_u8.shape:
             raise ValueError('generated %s and ground truth %s differ in shape' % (tuple(gen_u8.shape), tuple(gt_u8.shape)))
         self.n += gen_u8.shape[0]
-        if self.fid is not None:
+        if self.fid is not None and self.fid_device:
+            for b in self._fid_gen.push(gen_u8):
+                self._feat_gen.update(self.fid.features_u8(b.contiguous()))
+            if self._fid_gt is not None:
+                for b in self._fid_gt.push(gt_u8):
+                    self._feat_gt.update(self.fid.features_u8(b.contiguous()))
+        elif self.fid is not None:
             self._feat_gen += [self._features(b) for b in self._fid_gen.push(gen_u8)]
             if self._fid_gt is not None:
                 self._feat_gt += [self._features(b) for b in self._fid_gt.push(gt_u8)]
@@ -96,7 +112,17 @@ class Scorer(object):
                 self._pair(metrics, gen, gt, into)
 
     # ---- the totals: what was flushed plus the short last batch (the state is left as it is, so update() may go on)
+    def _moments(self, moments, batches):
+        """The device moments with the short last batch in: that batch goes into a COPY of the state."""
+        if batches.rest is not None:
+            moments = moments.copy().update(self.fid.features_u8(batches.rest.contiguous()))
+        if moments.n == 0:
+            raise ValueError('no images were given')
+        return moments
+
     def _statistics(self, feats, batches):
+        if self.fid_device:
+            return self._moments(feats, batches).statistics_host()
         feats = list(feats)
         if batches.rest is not None:
             feats.append(self._features(batches.rest))
@@ -120,7 +146,10 @@ class Scorer(object):
         if self.n == 0:
             raise ValueError('no images were given')
         out = {'n': self.n}
-        if self.fid is not None:
+        if self.fid is not None and self.fid_device:
+            ref = self.fid_reference if self.fid_reference is not None else self._moments(self._feat_gt, self._fid_gt).statistics()
+            out['fid'] = frechet_distance_device(*(self._moments(self._feat_gen, self._fid_gen).statistics() + tuple(ref)))
+        elif self.fid is not None:
             ref = self.fid_reference if self.fid_reference is not None else self._statistics(self._feat_gt, self._fid_gt)
             out['fid'] = calculate_frechet_distance(*(self.statistics() + tuple(ref)))
         into = (list(self._lpips_means), list(self._ssim), list(self._ms_ssim))

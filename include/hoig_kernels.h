@@ -815,6 +815,45 @@ int hoig_png_decode_u8(const uint8_t *bytes, int64_t nbytes, const hoig_png_deco
                        const hoig_png_decode_plan *plans_dev, int n, uint8_t *out, int64_t out_bytes, int32_t *status, void *workspace,
                        int64_t workspace_bytes, int bgr, hoig_stream_t stream);
 
+/* ---- STREAMING FID STATISTICS AND THE FRECHET DISTANCE IN FP64 (hoig_amd/csrc/fid_stats.hip, fid_stats.h, fid_stats_host.cpp;
+ *      hoig_amd/metrics/fid_device.py; docs/fid_device.md).  Matrices are row-major with explicit leading dimensions (in elements).
+ *      The *_host twins take host memory and make no HIP call; they walk every sum in the device's order. ---- */
+enum { HOIG_GEMM_ACCUMULATE = 1,  /* C += A^T B instead of C = A^T B */
+       HOIG_GEMM_SYMMETRIC = 2,   /* A == B (same pointer, M == N): only the tiles on and above the diagonal are computed, each element
+                                     is stored at its mirror place too (with ACCUMULATE, C is taken to be symmetric) */
+       HOIG_GEMM_F32 = 4          /* A and B hold fp32; element [k][c] enters as (double)x - pivot[c] (pivot: max(M, N) doubles, or
+                                     NULL for none) */ };
+/* C [M][N] (+)= A^T B for A [K][M] and B [K][N] on v_mfma_f64_16x16x4_f64; any M, N >= 1 and K >= 0.  One owner per element of C and
+ * a fixed order over K: no atomics, the result does not depend on scheduling.  Non-finite operands propagate by the IEEE rules.
+ * HOIG_EINVAL: a NULL pointer (A and B may be NULL when K is 0), a leading dimension below its row length, unknown flags, a pivot without HOIG_GEMM_F32. */
+int hoig_gemm_tn_f64(const void *A, int64_t lda, const void *B, int64_t ldb, const double *pivot, double *C, int64_t ldc, int M, int N,
+                     int K, int flags, hoig_stream_t stream);
+int hoig_gemm_tn_f64_host(const void *A, int64_t lda, const void *B, int64_t ldb, const double *pivot, double *C, int64_t ldc, int M,
+                          int N, int K, int flags);
+/* Rank-revealing pivoted Cholesky of the symmetric positive semi-definite S [D][D]: S = L L^T with L [D][rank] (row i of L belongs to
+ * row i of S: nothing is permuted in memory; piv[j] is the row step j took).  The pivot is the largest remaining diagonal entry, the
+ * lowest index on ties; the factorisation ends when that entry is <= D * 2^-52 * d0 or <= 0 (d0: the largest diagonal entry of S;
+ * d0 <= 0 gives rank 0).  info[0] = rank, info[1] = status: 0, or HOIG_EINVAL for a non-finite entry of S, in which case L, piv and
+ * info[0] are left as they are.  Columns [rank, D) of L and piv[rank ..] are left as they are too.
+ * Device: 3 + D launches on `stream` (a step that finds the factorisation finished returns at once); never synchronises, allocates
+ * nothing; info, piv, workspace (8-byte aligned, >= hoig_pchol_f64_workspace_bytes) in device memory.  The twin also RETURNS the status. */
+int64_t hoig_pchol_f64_workspace_bytes(int D);
+int hoig_pchol_f64(const double *S, int64_t lds, int D, double *L, int64_t ldl, int32_t *piv, int32_t *info, void *workspace,
+                   int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_pchol_f64_host(const double *S, int64_t lds, int D, double *L, int64_t ldl, int32_t *piv, int32_t *info);
+/* The eigenvalues of the symmetric A [n][n] (both triangles are read), ascending: unblocked Householder tridiagonalisation (three
+ * launches per step) in the workspace, then bisection on Sturm counts with Gershgorin bounds and dstebz's pivmin, one lane per
+ * eigenvalue, to a width of 2 * 2^-52 * |lambda|.  info[0] = status: 0, or HOIG_EINVAL for a non-finite entry (lambda is then left as
+ * it is).  The workspace holds, after its 32-byte header, the reduced matrix [n][n], then the tridiagonal's d [n] and e [n].
+ * hoig_tridiag_eigvals_f64: the bisection alone, on d [n] and e [n - 1]; hoig_sym_tridiag_f64_host: the twin's tridiagonal alone. */
+int64_t hoig_sym_eigvals_f64_workspace_bytes(int n);
+int hoig_sym_eigvals_f64(const double *A, int64_t lda, int n, double *lambda, int32_t *info, void *workspace, int64_t workspace_bytes,
+                         hoig_stream_t stream);
+int hoig_sym_eigvals_f64_host(const double *A, int64_t lda, int n, double *lambda, int32_t *info);
+int hoig_tridiag_eigvals_f64(const double *d, const double *e, int n, double *lambda, hoig_stream_t stream);
+int hoig_tridiag_eigvals_f64_host(const double *d, const double *e, int n, double *lambda);
+int hoig_sym_tridiag_f64_host(const double *A, int64_t lda, int n, double *d, double *e);
+
 #ifdef __cplusplus
 }
 #endif
