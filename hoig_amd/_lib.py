@@ -184,6 +184,15 @@ _SIGS = {
     'hoig_tridiag_eigvals_f64': [_vp, _vp, _i, _vp, _vp],
     'hoig_tridiag_eigvals_f64_host': [_vp, _vp, _i, _vp],
     'hoig_sym_tridiag_f64_host': [_vp, _i64, _i, _vp, _vp],
+    'hoig_grad_stats_chunk': [],
+    'hoig_grad_stats_max_grid': [],
+    'hoig_grad_stats': [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    'hoig_grad_stats_host': [_vp, _i64, _vp, _i, _vp, _vp, _vp],
+    'hoig_guard_decide': [_vp, _d, _d, _i, _vp, _vp, _vp],
+    'hoig_guard_decide_host': [_vp, _d, _d, _i, _vp, _vp],
+    'hoig_adam_tick_guarded': [_vp, _vp, _vp, _vp],
+    'hoig_adam_step_dev_guarded': [_vp, _vp, _vp, _vp, _i64, _vp, _f, _vp, _vp],
+    'hoig_adam_pack_step_guarded': [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 
@@ -231,6 +240,8 @@ def _load():
     lib.hoig_pchol_f64_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_sym_eigvals_f64_workspace_bytes.argtypes = [_i]
     lib.hoig_sym_eigvals_f64_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_grad_stats_workspace_bytes.argtypes = [_i64, _i]
+    lib.hoig_grad_stats_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
     lib.hoig_jpeg_decode_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_par_workspace_bytes.argtypes = [_vp, _i, _i]
@@ -245,6 +256,10 @@ def _load():
 
 
 lib = _load()
+
+GUARD_SKIP = 1                                   # HOIG_GUARD_SKIP
+GRAD_CHUNK = lib.hoig_grad_stats_chunk()         # HOIG_GRAD_CHUNK: elements of a stage-1 chunk of hoig_grad_stats
+GRAD_MAX_GRID = lib.hoig_grad_stats_max_grid()   # the most workgroups its stage 1 uses
 
 
 def set_tuning(key, value):

@@ -371,12 +371,19 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const float *__restrict__
 // channels (float4 of p, g, m, v; the arithmetic of adam_dev_kernel, expression for expression) and writes their forward planes
 // as 8-byte stores; the data-gradient planes go through the same LDS transpose, four output channels per thread.  Workgroups
 // past the tile count do the plain update of the parameters that have no planes (`plain`: 1024-element chunks).
+// GUARD (hoig_adam_pack_step_guarded, docs/grad_guard.md): `guard` = {scale, skip}; a skipped step returns before the first load (the
+// whole workgroup does: no barrier is left waiting), otherwise the gradient's factor is gscale * guard[0].
+template <bool GUARD>
 __global__ __launch_bounds__(256) void adam_pack_kernel(float *__restrict__ flat, const float *__restrict__ grad, float *__restrict__ m_,
                                                         float *__restrict__ v_, const float *__restrict__ derived, float gscale,
                                                         const int64_t *__restrict__ segs, int nseg, int64_t ntiles,
                                                         const int64_t *__restrict__ plain, unsigned short *__restrict__ hi_f,
                                                         unsigned short *__restrict__ lo_f, unsigned short *__restrict__ hi_d,
-                                                        unsigned short *__restrict__ lo_d) {
+                                                        unsigned short *__restrict__ lo_d, const float *__restrict__ guard) {
+    if constexpr (GUARD) {
+        if (guard[1] != 0.f) return;
+        gscale = gscale * guard[0];
+    }
     const float step_size = derived[0], omb1 = derived[1], b2 = derived[2], omb2 = derived[3], eps = derived[4], bc2_sqrt = derived[5];
     struct Q { float4 p, g, m, v; };
     auto load4 = [&](int64_t i) -> Q {
@@ -1627,8 +1634,23 @@ extern "C" int hoig_adam_pack_step(float *flat, const float *grad, float *exp_av
     if (!flat || !grad || !exp_avg || !exp_avg_sq || !derived || !segs || nseg <= 0 || ntiles <= 0 || nplain < 0 || (nplain && !plain) ||
         !hi_f || !lo_f || !hi_d || !lo_d)
         return HOIG_EINVAL;
-    adam_pack_kernel<<<(unsigned)(ntiles + nplain), 256, 0, (hipStream_t)stream>>>(flat, grad, exp_avg, exp_avg_sq, derived, grad_scale, segs,
-                                                                                 nseg, ntiles, plain, hi_f, lo_f, hi_d, lo_d);
+    adam_pack_kernel<false><<<(unsigned)(ntiles + nplain), 256, 0, (hipStream_t)stream>>>(flat, grad, exp_avg, exp_avg_sq, derived, grad_scale,
+                                                                                        segs, nseg, ntiles, plain, hi_f, lo_f, hi_d, lo_d,
+                                                                                        nullptr);
+    HOIG_LAUNCH_CHECK();
+    return HOIG_OK;
+}
+
+extern "C" int hoig_adam_pack_step_guarded(float *flat, const float *grad, float *exp_avg, float *exp_avg_sq, const float *derived,
+                                           float grad_scale, const int64_t *segs, int nseg, int64_t ntiles, const int64_t *plain,
+                                           int64_t nplain, uint16_t *hi_f, uint16_t *lo_f, uint16_t *hi_d, uint16_t *lo_d,
+                                           const float *guard, hoig_stream_t stream) {
+    if (!flat || !grad || !exp_avg || !exp_avg_sq || !derived || !segs || nseg <= 0 || ntiles <= 0 || nplain < 0 || (nplain && !plain) ||
+        !hi_f || !lo_f || !hi_d || !lo_d || !guard)
+        return HOIG_EINVAL;
+    adam_pack_kernel<true><<<(unsigned)(ntiles + nplain), 256, 0, (hipStream_t)stream>>>(flat, grad, exp_avg, exp_avg_sq, derived, grad_scale,
+                                                                                       segs, nseg, ntiles, plain, hi_f, lo_f, hi_d, lo_d,
+                                                                                       guard);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

@@ -481,8 +481,14 @@ __global__ __launch_bounds__(NT) void adam_kernel(float *__restrict__ p, const f
 // captured hipGraph: `state` = {lr, beta1, beta2, eps, step} (doubles; the host only rewrites lr), `derived` = the six fp32
 // scalars adam_kernel takes by value.  One thread: advance the step count and evaluate the bias corrections in double, as
 // hoig_adam_step does on the host.
-__global__ void adam_tick_kernel(double *__restrict__ state, float *__restrict__ derived) {
+// GUARD (the *_guarded entry points, docs/grad_guard.md): `guard` = {scale, skip} as hoig_guard_decide left it; a skipped step leaves
+// the count and `derived` as they are.
+template <bool GUARD>
+__global__ void adam_tick_kernel(double *__restrict__ state, float *__restrict__ derived, const float *__restrict__ guard) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if constexpr (GUARD) {
+        if (guard[1] != 0.f) return;
+    }
     const double lr = state[0], b1 = state[1], b2 = state[2], eps = state[3];
     const double step = state[4] + 1.0;
     state[4] = step;
@@ -495,9 +501,15 @@ __global__ void adam_tick_kernel(double *__restrict__ state, float *__restrict__
     derived[5] = (float)sqrt(bc2);
 }
 
+// GUARD: a skipped step returns before the first load; otherwise the gradient's factor is gscale * guard[0] (guard[0] = 1.0f: gscale's bits)
+template <bool GUARD>
 __global__ __launch_bounds__(NT) void adam_dev_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                       float *__restrict__ v, int64_t n, const float *__restrict__ derived,
-                                                      float gscale) {
+                                                      float gscale, const float *__restrict__ guard) {
+    if constexpr (GUARD) {
+        if (guard[1] != 0.f) return;
+        gscale = gscale * guard[0];
+    }
     const float step_size = derived[0], omb1 = derived[1], b2 = derived[2], omb2 = derived[3], eps = derived[4],
                 bc2_sqrt = derived[5];
     const int64_t n4 = n >> 2;
@@ -754,14 +766,27 @@ extern "C" int hoig_adam_step(float *param, const float *grad, float *exp_avg, f
 }
 extern "C" int hoig_adam_tick(double *state, float *derived, hoig_stream_t stream) {
     if (!state || !derived) return HOIG_EINVAL;
-    adam_tick_kernel<<<1, 64, 0, ST>>>(state, derived);
+    adam_tick_kernel<false><<<1, 64, 0, ST>>>(state, derived, nullptr);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }
 extern "C" int hoig_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                   const float *derived, float grad_scale, hoig_stream_t stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !derived) return HOIG_EINVAL;
-    adam_dev_kernel<<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale);
+    adam_dev_kernel<false><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, nullptr);
+    HOIG_LAUNCH_CHECK();
+    return HOIG_OK;
+}
+extern "C" int hoig_adam_tick_guarded(double *state, float *derived, const float *guard, hoig_stream_t stream) {
+    if (!state || !derived || !guard) return HOIG_EINVAL;
+    adam_tick_kernel<true><<<1, 64, 0, ST>>>(state, derived, guard);
+    HOIG_LAUNCH_CHECK();
+    return HOIG_OK;
+}
+extern "C" int hoig_adam_step_dev_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                          const float *derived, float grad_scale, const float *guard, hoig_stream_t stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !derived || !guard) return HOIG_EINVAL;
+    adam_dev_kernel<true><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, guard);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

@@ -100,6 +100,21 @@ class Trainer(BaseModel):
         self._static_inputs = {}         # input signature -> the staged tensors a captured step reads
         self._sig = None
 
+        # the gradient guard (docs/grad_guard.md), off by default: opt.grad_guard / HOIG_GRAD_GUARD = 'off' | 'watch' | 'skip';
+        # opt.max_grad_norm_G / _D > 0 clip the network's gradient to that global 2-norm.  Checked here, not in the middle of a step.
+        self._guard_policy = str(getattr(opt, 'grad_guard', None) or os.environ.get('HOIG_GRAD_GUARD', '') or 'off').lower()
+        if self._guard_policy not in ('off', 'watch', 'skip'):
+            raise ValueError("grad_guard %r ('off' | 'watch' | 'skip')" % (self._guard_policy,))
+        self._guard_norms = {}
+        for tag in ('G', 'D'):
+            v = float(getattr(opt, 'max_grad_norm_' + tag, 0.0) or 0.0)
+            if not v >= 0.0:
+                raise ValueError('max_grad_norm_%s %r must be >= 0 (0: no clipping)' % (tag, v))
+            self._guard_norms[tag] = v
+        if self._guard_policy == 'off' and (any(self._guard_norms.values()) or getattr(opt, 'grad_stats_per_tensor', False)):
+            raise ValueError("max_grad_norm_G / max_grad_norm_D / grad_stats_per_tensor need grad_guard 'watch' or 'skip'")
+        self._guards = {}                # 'G' / 'D' -> GradGuard; empty with the option off
+
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
             self._init_train_vars()
@@ -171,6 +186,12 @@ class Trainer(BaseModel):
                                       betas=(self._opt.G_adam_b1, self._opt.G_adam_b2))
         self._optimizer_D = FusedAdam(self._net(self._D), lr=self._current_lr_D,
                                       betas=(self._opt.D_adam_b1, self._opt.D_adam_b2))
+        if self._guard_policy != 'off':
+            from ..guard import GradGuard
+            per_tensor = bool(getattr(self._opt, 'grad_stats_per_tensor', False))
+            for tag, net in (('G', self._G), ('D', self._D)):
+                self._guards[tag] = GradGuard(self._net(net), policy=self._guard_policy, max_norm=self._guard_norms[tag],
+                                              per_tensor=per_tensor)
 
     def _init_prefetch_inputs(self):
         self._real_src = self._real_tsf = self._bg_mask = self._hand_mask = None
@@ -496,8 +517,15 @@ class Trainer(BaseModel):
         ddp = isinstance(net, FlatDDP) and net.sync.active
         tree = self._net(net)
 
+        guard = self._guards.get('G' if net is self._G else 'D')
+
         def run():
-            if ddp:           # Adam of slice i runs while slices i+1.. are still being exchanged
+            if guard is not None:      # (under an exchange the guarded step drains the slices first: the decision needs them all)
+                if ddp:
+                    optimizer.step(grad_scale=1.0 / net.sync.world, ready=net.sync.iter_all_reduce(), guard=guard)
+                else:
+                    optimizer.step(guard=guard)
+            elif ddp:         # Adam of slice i runs while slices i+1.. are still being exchanged
                 optimizer.step(grad_scale=1.0 / net.sync.world, ready=net.sync.iter_all_reduce())
             else:
                 optimizer.step()
@@ -696,7 +724,19 @@ class Trainer(BaseModel):
                             ('d_fake', self._d_fake.item())])
 
     def get_current_scalars(self):
-        return OrderedDict([('lr_G', self._current_lr_G), ('lr_D', self._current_lr_D)])
+        out = OrderedDict([('lr_G', self._current_lr_G), ('lr_D', self._current_lr_D)])
+        for tag, guard in self._guards.items():       # (a logging tick: GradGuard.report() copies to the host)
+            r = guard.report()
+            out['grad_norm_' + tag], out['grad_max_' + tag] = r['norm'], r['max']
+            out['skipped_' + tag], out['clipped_' + tag] = r['skipped'], r['clipped']
+        return out
+
+    def grad_report(self):
+        """{'G' | 'D': {reference parameter name: (gradient norm, max |g|, non-finite count)}} of the last step
+        (opt.grad_stats_per_tensor; copies to the host)."""
+        if not self._guards:
+            raise RuntimeError("grad_report(): grad_guard is 'off'")
+        return OrderedDict((tag, guard.per_tensor()) for tag, guard in self._guards.items())
 
     def get_current_visuals(self):
         self._flush_input_checks()

@@ -425,7 +425,10 @@ class FusedAdam(object):
     The schedule lives in DEVICE memory ({lr, beta1, beta2, eps, step}: hoig_adam_tick advances the step count and derives the
     bias corrections there), so a step is a pure function of device state and can be captured in a hipGraph
     (Trainer._graph_step).  ``param_groups`` / ``step_count`` are the host's view: a change made on the host (a new learning
-    rate, a loaded checkpoint) is uploaded before the next step; a replayed step is reported with ``replayed()``."""
+    rate, a loaded checkpoint) is uploaded before the next step; a replayed step is reported with ``replayed()``.
+
+    ``step(guard=...)`` (hoig_amd.guard.GradGuard, docs/grad_guard.md): the device decides whether the step happens, so the device's
+    count is the authority and the host's is brought in line where the host synchronises anyway (``reconcile_step()``)."""
 
     def __init__(self, tree, lr, betas=(0.9, 0.999), eps=1e-8):
         self.tree = tree
@@ -438,6 +441,8 @@ class FusedAdam(object):
         self._state = torch.zeros(5, dtype=torch.float64, device=tree.flat.device)
         self._derived = torch.zeros(8, dtype=torch.float32, device=tree.flat.device)
         self._on_device = None          # the host values self._state was last written from
+        self._count_stale = False       # steps ran under a guard since the count was last read: the device may have skipped some
+        self._guarded = False           # the last step() ran under a guard (a replay of its capture does too: replayed())
 
     def zero_grad(self, set_to_none=False):
         join_wgrad_streams()
@@ -455,8 +460,23 @@ class FusedAdam(object):
             from . import ops
             if ops.capturing():
                 raise RuntimeError('FusedAdam: the optimiser schedule changed while a hipGraph was being captured')
+            if self._count_stale and self._on_device is not None and want[4] == self._on_device[4]:
+                # under a guard the device's count is the authority: a new learning rate goes up with the count the device holds,
+                # not with a host count that includes skipped steps
+                self.reconcile_step()
+                want = self._host_state()
             self._state.copy_(torch.tensor(want, dtype=torch.float64))
             self._on_device = want
+
+    def reconcile_step(self):
+        """Under a guard the device decides whether a step counts (hoig_adam_tick_guarded), and the host only assumes that it did.
+        Read the device's count back (synchronises) -- called where the host synchronises anyway: state_dict(), sync_state() when the
+        schedule changed, GradGuard.report()."""
+        if self._count_stale and self._on_device is not None:
+            self.tree.wait_pending()                  # (the step may still be running on a side stream)
+            self.step_count = int(self._state[4].item())
+            self._on_device = self._on_device[:4] + (float(self.step_count),)
+        self._count_stale = False
 
     def captured_packs(self):
         """Right after a step of this optimiser was CAPTURED: (did the capture re-pack the operand planes?, the fp6 records?).  The
@@ -474,6 +494,8 @@ class FusedAdam(object):
         stale from here on and re-made by whoever asks next."""
         self.step_count += 1
         self._on_device = self._on_device[:4] + (float(self.step_count),)
+        if self._guarded:              # (a replayed guarded step may have been skipped on the device: reconcile_step)
+            self._count_stale = True
         tree = self.tree
         tree.version += 1
         if planes:
@@ -481,10 +503,14 @@ class FusedAdam(object):
         if records and tree._f6 is not None:
             tree._f6['version'] = tree.version
 
-    def step(self, grad_scale=1.0, ready=None):
+    def step(self, grad_scale=1.0, ready=None, guard=None):
         """One Adam step over the flat buffers.  `ready` (DDP): an iterator of (begin, end) element ranges whose gradients
         have just been exchanged -- the update of a range is launched as soon as it is yielded, so Adam pipelines behind
-        the sliced all-reduce instead of waiting for the last slice (GradSync.iter_all_reduce)."""
+        the sliced all-reduce instead of waiting for the last slice (GradSync.iter_all_reduce).
+        `guard` (hoig_amd.guard.GradGuard): the step obeys the guard's device-side decision (docs/grad_guard.md)."""
+        if guard is not None:
+            return self._guarded_step(grad_scale, ready, guard)
+        self._guarded = False
         self.sync_state()
         join_wgrad_streams()
         L.call('hoig_adam_tick', _p(self._state), _p(self._derived), _st())
@@ -505,7 +531,45 @@ class FusedAdam(object):
                    v.data_ptr() + 4 * a, b - a, _p(self._derived), grad_scale, _st())
         self.tree.version += 1
 
+    def _guarded_step(self, grad_scale, ready, guard):
+        """step() under a guard: statistics and decision, then the guarded tick and update -- the same three routes (fused planes,
+        two launches, slices).  The decision needs the WHOLE reduced gradient, so an exchange is drained first (every rank reads the
+        same reduced buffer and decides the same; Adam no longer pipelines behind the slices), and the slices are updated afterwards.
+        The host counts the step as taken; reconcile_step() corrects it from the device."""
+        self.sync_state()
+        join_wgrad_streams()
+        slices = list(ready) if ready is not None else None
+        guard.attach(self)
+        guard.observe(pre_scale=grad_scale)
+        gp = _p(guard.guard)
+        L.call('hoig_adam_tick_guarded', _p(self._state), _p(self._derived), gp, _st())
+        self.step_count += 1
+        self._on_device = self._on_device[:4] + (float(self.step_count),)
+        self._count_stale = self._guarded = True
+        fl, gr, m, v = self.tree.flat, self.tree.flat_grad, self.exp_avg, self.exp_avg_sq
+        fused = self.tree.fused_step_tables() if (slices is None and self.fuse_planes) else None
+        if fused is not None:
+            table, ntiles, plain, nplain, b = fused
+            L.call('hoig_adam_pack_step_guarded', _p(fl), _p(gr), _p(m), _p(v), _p(self._derived), grad_scale, _p(table),
+                   table.shape[0], ntiles, _p(plain), nplain, _p(b[0]), _p(b[1]), _p(b[2]), _p(b[3]), gp, _st())
+            # A taken step rewrote every plane; a skipped one wrote nothing, and the host cannot tell which.  So the planes count as
+            # current only if they were current before (a skipped step leaves weights and planes in line) or the step cannot be
+            # skipped (policy 'watch'); planes that were stale stay stale and the next forward re-packs them -- once too often after
+            # a taken step, never too rarely.
+            current = self.tree._plane_version == self.tree.version or not (guard.flags & L.GUARD_SKIP)
+            self.tree.version += 1
+            if current:
+                self.tree._plane_version = self.tree.version
+            return
+        for a, b in (slices if slices is not None else [(0, fl.numel())]):
+            L.call('hoig_adam_step_dev_guarded', fl.data_ptr() + 4 * a, gr.data_ptr() + 4 * a, m.data_ptr() + 4 * a,
+                   v.data_ptr() + 4 * a, b - a, _p(self._derived), grad_scale, gp, _st())
+        # (the version is bumped on every route whether or not the device took the step: after a skipped one the planes and fp6
+        #  records are re-packed from unchanged weights -- a needless launch, never a stale operand)
+        self.tree.version += 1
+
     def state_dict(self):
+        self.reconcile_step()
         state = {}
         if self.step_count > 0:
             ms = self.tree.export_dict(self.exp_avg)
@@ -529,5 +593,6 @@ class FusedAdam(object):
         self.tree.import_dict(self.exp_avg, ms, strict=False)
         self.tree.import_dict(self.exp_avg_sq, vs, strict=False)
         self.step_count = steps.pop() if steps else 0
+        self._count_stale = False       # (the loaded count goes up to the device with the next sync_state)
         g = sd['param_groups'][0]
         self.param_groups[0].update(lr=g['lr'], betas=tuple(g['betas']), eps=g['eps'])

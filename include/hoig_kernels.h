@@ -854,6 +854,48 @@ int hoig_tridiag_eigvals_f64(const double *d, const double *e, int n, double *la
 int hoig_tridiag_eigvals_f64_host(const double *d, const double *e, int n, double *lambda);
 int hoig_sym_tridiag_f64_host(const double *A, int64_t lda, int n, double *d, double *e);
 
+/* ---- GRADIENT GUARD: STATISTICS, SKIP-STEP AND NORM CLIPPING ON THE DEVICE (hoig_amd/csrc/grad_guard.hip, grad_guard.h,
+ *      grad_guard_host.cpp; hoig_amd/guard.py; docs/grad_guard.md).  The *_host twins take host memory, make no HIP call and walk
+ *      every sum in the device's order: their results are the device's, bit for bit. ---- */
+#define HOIG_GRAD_CHUNK 4096          /* elements of a stage-1 chunk (hoig_grad_stats_chunk() returns it) */
+enum { HOIG_GUARD_SKIP = 1 };         /* hoig_guard_decide: a non-finite gradient skips the update (without it, it is only counted) */
+int hoig_grad_stats_chunk(void);
+int hoig_grad_stats_max_grid(void);   /* the most workgroups stage 1 uses: a longer buffer is walked in several rounds */
+/* Statistics of the fp32 buffer x[0 .. n), for the whole of it (total[3]) and for each of the nseg rows {first, count} of a table
+ * (seg_out[nseg][3]): {sum x^2 over the finite elements, max |x| over the finite elements, the number of non-finite elements}, doubles,
+ * the count exact.  Rows are int64, sorted, disjoint, count >= 1, inside [0, n); gaps are allowed.  Squares and sums are fp64 and the
+ * order of the additions is a function of (n, table) alone (grad_guard.h); `total` does not depend on the table at all.
+ * The table is given twice, as for the PNG decoder's plans: segs_host is read at the call (HOIG_EINVAL for n <= 0, a bad table, a NULL
+ * or misaligned pointer: nothing is launched, the outputs stay as they are), segs_dev is the same rows in device memory, read by the
+ * kernels.  Only segs_host is checked: THE CALLER GUARANTEES THAT THE TWO COPIES HOLD THE SAME ROWS.  (The kernels clamp every piece to
+ * its chunk and every row's slots to the workspace, so a differing device copy gives wrong statistics, not an access outside x or the
+ * workspace; seg_out is indexed by the row number alone.)  x, seg_out, total and workspace (8-byte aligned, >= hoig_grad_stats_workspace_bytes(n, nseg); < 0: invalid) are device
+ * memory.  Two launches on `stream`; never synchronises, allocates nothing. */
+int64_t hoig_grad_stats_workspace_bytes(int64_t n, int nseg);
+int hoig_grad_stats(const float *x, int64_t n, const int64_t *segs_host, const int64_t *segs_dev, int nseg, double *seg_out,
+                    double *total, void *workspace, hoig_stream_t stream);
+int hoig_grad_stats_host(const float *x, int64_t n, const int64_t *segs, int nseg, double *seg_out, double *total, void *workspace);
+/* The decision, one thread: norm = pre_scale * sqrt(total[0]) in double.  guard[1] (skip) = 1.0f when total[2] > 0 and flags has
+ * HOIG_GUARD_SKIP, else 0.0f; guard[0] (scale) = 1.0f, or (float)(max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s
+ * coefficient -- when max_norm > 0, total[2] == 0 and norm > max_norm.  record[7] (doubles, the caller zeroes it once): steps seen,
+ * steps skipped, steps clipped, the last norm, the last pre_scale * max |x|, the last non-finite count, the largest finite norm seen.
+ * HOIG_EINVAL: a NULL pointer, unknown flags, pre_scale <= 0, max_norm < 0. */
+int hoig_guard_decide(const double *total, double pre_scale, double max_norm, int flags, float *guard, double *record,
+                      hoig_stream_t stream);
+int hoig_guard_decide_host(const double *total, double pre_scale, double max_norm, int flags, float *guard, double *record);
+/* The device-schedule Adam entry points under a guard = {scale, skip} (two floats in device memory, written by hoig_guard_decide).
+ * skip != 0: the tick leaves state[4] and `derived` as they are (as torch's GradScaler leaves the step count), the step kernels
+ * return without touching a parameter, a moment or an operand plane.  Otherwise the gradient is read as g * (grad_scale * guard[0]);
+ * with guard = {1.0f, 0.0f} the results are those of the unguarded entry points bit for bit.  The same kernel bodies, instantiated
+ * with a template flag.  The host-schedule hoig_adam_step has no guarded form: a guard's decision exists on the device only. */
+int hoig_adam_tick_guarded(double *state, float *derived, const float *guard, hoig_stream_t stream);
+int hoig_adam_step_dev_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *derived,
+                               float grad_scale, const float *guard, hoig_stream_t stream);
+int hoig_adam_pack_step_guarded(float *flat, const float *grad, float *exp_avg, float *exp_avg_sq, const float *derived,
+                                float grad_scale, const int64_t *segs, int nseg, int64_t ntiles, const int64_t *plain, int64_t nplain,
+                                uint16_t *hi_f, uint16_t *lo_f, uint16_t *hi_d, uint16_t *lo_d, const float *guard,
+                                hoig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-"""Optimiser step + operand-plane refresh of the generator's flat buffer, timed alone: FusedAdam.fuse_planes False (two launches) / True."""
+"""Optimiser step + operand-plane refresh of the generator's flat buffer, timed alone: FusedAdam.fuse_planes False (two launches) / True,
+each without and with a gradient guard (GradGuard.observe() + the guarded tick and update: docs/grad_guard.md)."""
 import os
 import sys
 
@@ -16,15 +17,18 @@ m.optimize_parameters()
 opt = m._optimizer_G
 tree = opt.tree
 print('parameters %.1f M, plane tiles %d, plain chunks %d' % (tree.flat.numel() / 1e6, tree._plane_tiles, tree._plain_chunks[1]))
+from hoig_amd.guard import GradGuard                      # noqa: E402
+guard = GradGuard(tree, policy='skip', max_norm=1.0)
 for r in range(3):
     for v in (0, 1):
-        opt.fuse_planes = bool(v)
-        opt.step(); tree._refresh_planes()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            opt.step()
-            tree._refresh_planes()
-        e1.record()
-        torch.cuda.synchronize()
-        print('fuse_planes=%d  %.1f us per step + refresh' % (v, e0.elapsed_time(e1) * 100), flush=True)
+        for kw in ({}, dict(guard=guard)):
+            opt.fuse_planes = bool(v)
+            opt.step(**kw); tree._refresh_planes()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                opt.step(**kw)
+                tree._refresh_planes()
+            e1.record()
+            torch.cuda.synchronize()
+            print('fuse_planes=%d guard=%d  %.1f us per step + refresh' % (v, bool(kw), e0.elapsed_time(e1) * 100), flush=True)
