@@ -193,6 +193,11 @@ _SIGS = {
     'hoig_adam_tick_guarded': [_vp, _vp, _vp, _vp],
     'hoig_adam_step_dev_guarded': [_vp, _vp, _vp, _vp, _i64, _vp, _f, _vp, _vp],
     'hoig_adam_pack_step_guarded': [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    'hoig_ema_tick': [_vp, _vp, _vp, _vp],
+    'hoig_ema_tick_host': [_vp, _vp, _vp],
+    'hoig_ema_update': [_vp, _vp, _i64, _vp, _vp, _vp],
+    'hoig_ema_update_host': [_vp, _vp, _i64, _vp, _vp],
+    'hoig_swap_f32': [_vp, _vp, _i64, _vp],
 }
 
 

@@ -12,6 +12,7 @@ model and the per-object renderer buffers -- assets the reference does not ship 
 hoig_amd/hand_recovery.py runs ``HandRecoveryFlow.forward``, trainer.py:46-145, as three device stages) -- or images + rasteriser
 outputs, or the prepared tensors that stage produces (the a2 surface: a dict with the keys of ``hoig_amd.synthetic.make_inputs``).
 """
+import contextlib
 import math
 import os
 import sys
@@ -25,7 +26,7 @@ from .. import _lib, ops
 from ..options import is_dexycb
 from ..ddp import FlatDDP
 from ..nn import FusedAdam
-from .base_model import BaseModel
+from .base_model import BaseModel, strip_ddp_prefix
 from .networks import NetworksFactory
 from .networks.generator import to_nhwc, as_nchw, forks_streams as generator_forks_streams
 from .networks.vgg19 import Vgg19, VGGLoss
@@ -77,6 +78,8 @@ class Trainer(BaseModel):
     _use_graph = False
     _static_inputs = None
     _sig = None
+    _ema = None               # (class defaults: a model assembled without __init__, as bench.py's forward leg is, keeps no average)
+    _eval_ema = False
 
     def __init__(self, opt, use_ddp=False):
         super(Trainer, self).__init__(opt, use_ddp)
@@ -114,6 +117,11 @@ class Trainer(BaseModel):
         if self._guard_policy == 'off' and (any(self._guard_norms.values()) or getattr(opt, 'grad_stats_per_tensor', False)):
             raise ValueError("max_grad_norm_G / max_grad_norm_D / grad_stats_per_tensor need grad_guard 'watch' or 'skip'")
         self._guards = {}                # 'G' / 'D' -> GradGuard; empty with the option off
+        # the EMA of G's weights (docs/ema.md), off by default: opt.ema_decay / HOIG_EMA_DECAY in (0, 1), opt.ema_warmup (True);
+        # opt.eval_ema / HOIG_EVAL_EMA: an eval-mode forward runs on the average (an eval-only model loads the saved one as G)
+        from ..ema import parse_options as parse_ema_options
+        self._ema_decay, self._ema_warmup, self._eval_ema = parse_ema_options(opt, self._is_train)
+        self._ema = None                 # EmaWeights of G; None with the option off, and in an eval-only model
 
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
@@ -122,6 +130,8 @@ class Trainer(BaseModel):
 
         if self._opt.load_path != 'None' and self._opt.load_path is not None:
             self._load_params(self._G, self._opt.load_path, need_module=False)
+            if self._ema is not None:
+                self._ema.reset()        # (the average starts from the loaded generator)
         elif not self._is_train or self._opt.load_epoch > 0:
             self.load()
 
@@ -192,6 +202,9 @@ class Trainer(BaseModel):
             for tag, net in (('G', self._G), ('D', self._D)):
                 self._guards[tag] = GradGuard(self._net(net), policy=self._guard_policy, max_norm=self._guard_norms[tag],
                                               per_tensor=per_tensor)
+        if self._ema_decay is not None:
+            from ..ema import EmaWeights
+            self._ema = EmaWeights(self._net(self._G), self._ema_decay, warmup=self._ema_warmup)
 
     def _init_prefetch_inputs(self):
         self._real_src = self._real_tsf = self._bg_mask = self._hand_mask = None
@@ -380,14 +393,32 @@ class Trainer(BaseModel):
         D step ended: its exchange (28 MB) + Adam have that long to finish on the side stream."""
         self._net(self._D).wait_pending()
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the scope G's weights are their moving average (EmaWeights.swapped(), docs/ema.md): exchanged in place on entry and
+        back on exit.  Not inside optimize_parameters(), and not while a step is being captured."""
+        if self._ema is None:
+            raise RuntimeError('ema_weights(): no average is kept (opt.ema_decay / HOIG_EMA_DECAY is off, or the model is eval-only)')
+        with self._ema.swapped():
+            try:
+                yield self._ema
+            finally:
+                self._join_backward_streams()        # (the branch streams of a forward in the scope, before the weights go back)
+
     def forward(self, keep_data_for_visuals=False, return_estimates=False):
         if not self._is_train and not torch.is_grad_enabled():
-            # generator-only inference (eval.py:59-65; BASELINE.json configs[4]): no backward follows, so the forward may run on the
-            # arithmetic that is bounded by north_star's output tolerance alone (opt.eval_precision, default 'f16f6'; 'same': the
-            # training forward's)
-            with ops.inference_forward_precision(getattr(self._opt, 'eval_precision', os.environ.get('HOIG_EVAL_PRECISION', 'f16f6'))):
-                return self._forward(keep_data_for_visuals)
+            if self._eval_ema and self._ema is not None and not self._ema.active:
+                with self.ema_weights():
+                    return self._eval_forward(keep_data_for_visuals)
+            return self._eval_forward(keep_data_for_visuals)
         return self._forward(keep_data_for_visuals)
+
+    def _eval_forward(self, keep_data_for_visuals=False):
+        # generator-only inference (eval.py:59-65; BASELINE.json configs[4]): no backward follows, so the forward may run on the
+        # arithmetic that is bounded by north_star's output tolerance alone (opt.eval_precision, default 'f16f6'; 'same': the
+        # training forward's)
+        with ops.inference_forward_precision(getattr(self._opt, 'eval_precision', os.environ.get('HOIG_EVAL_PRECISION', 'f16f6'))):
+            return self._forward(keep_data_for_visuals)
 
     def _forward(self, keep_data_for_visuals=False):
         self._wait_g()
@@ -529,6 +560,8 @@ class Trainer(BaseModel):
                 optimizer.step(grad_scale=1.0 / net.sync.world, ready=net.sync.iter_all_reduce())
             else:
                 optimizer.step()
+            if self._ema is not None and net is self._G:      # behind the (last slice's) Adam, on its stream, under its guard
+                self._ema.update(guard=guard)
             tree.refresh_planes()      # off the next forward's critical path
 
         if not overlap:
@@ -821,6 +854,11 @@ class Trainer(BaseModel):
         self._save_network(self._D, 'D', label)
         self._save_optimizer(self._optimizer_G, 'G', label)
         self._save_optimizer(self._optimizer_D, 'D', label)
+        if self._ema is not None:
+            # a plain G state dict (eval.py loads it through --load_path; the label still parses as split('_')[2]) and its schedule
+            sd = self._ema.state_dict(prefix='module.' if isinstance(self._G, FlatDDP) else '')      # (G's own keys)
+            print('saved net: %s' % self._ckpt.write(sd, 'net', label, 'G_ema'))
+            self._ckpt.write(dict(updates=self._ema.updates(), decay=self._ema.decay, warmup=self._ema.warmup), 'opt', label, 'G_ema')
 
     def load(self):
         """HOIG_HOv3/models/trainer.py:562-575; the HOIG_DexYCB copy (its trainer.py:558-573) differs twice: it hands the file's
@@ -829,7 +867,11 @@ class Trainer(BaseModel):
         file is overridden)."""
         load_epoch = self._opt.load_epoch
         need_module = self._dexycb
-        self._load_network(self._G, 'G', load_epoch, need_module=need_module)
+        if not self._is_train and self._eval_ema:
+            # an eval-only model takes the saved average AS its generator: no second buffer (a missing file: FileNotFoundError)
+            self._load_network(self._G, 'G_ema', load_epoch, need_module=need_module)
+        else:
+            self._load_network(self._G, 'G', load_epoch, need_module=need_module)
         if self._is_train:
             self._load_network(self._D, 'D', load_epoch, need_module=need_module)
             self._load_optimizer(self._optimizer_G, 'G', load_epoch)
@@ -838,6 +880,24 @@ class Trainer(BaseModel):
             if self._dexycb and no_decay is not None and load_epoch > no_decay:
                 for _ in range(no_decay, load_epoch):
                     self.update_learning_rate()
+            if self._ema is not None:
+                self._load_ema(load_epoch)
+
+    def _load_ema(self, load_epoch):
+        quiet = dist.is_available() and dist.is_initialized() and dist.get_rank() != 0
+        net_path, opt_path = self._ckpt.file('net', load_epoch, 'G_ema'), self._ckpt.file('opt', load_epoch, 'G_ema')
+        if not (os.path.isfile(net_path) and os.path.isfile(opt_path)):
+            self._ema.reset()
+            if not quiet:
+                print('no EMA checkpoint %s: the average starts from the loaded G, 0 updates' % net_path)
+            return
+        meta = self._ckpt.read(opt_path)
+        self._ema.load_state_dict(strip_ddp_prefix(self._ckpt.read(net_path)), int(meta['updates']))
+        for key, mine in (('decay', self._ema.decay), ('warmup', self._ema.warmup)):
+            if meta.get(key) != mine and not quiet:
+                print('EMA checkpoint %s was written with %s %r; continuing with %r' % (opt_path, key, meta.get(key), mine))
+        if not quiet:
+            print('loaded EMA: %s (%d updates)' % (net_path, int(meta['updates'])))
 
     def update_learning_rate(self):
         """One linear decay step towards final_lr for both optimisers (trainer.py:577-591).  The new rates reach the device-

@@ -896,6 +896,23 @@ int hoig_adam_pack_step_guarded(float *flat, const float *grad, float *exp_avg, 
                                 uint16_t *hi_f, uint16_t *lo_f, uint16_t *hi_d, uint16_t *lo_d, const float *guard,
                                 hoig_stream_t stream);
 
+/* ---- EMA OF A NETWORK'S WEIGHTS ON THE DEVICE (hoig_amd/csrc/ema.hip, ema.h, ema_host.cpp; hoig_amd/ema.py; docs/ema.md).  The
+ *      *_host twins take host memory, make no HIP call and run the same inline functions: their results are the device's, bit for
+ *      bit.  `guard` is NULL or the {scale, skip} pair of hoig_guard_decide; only skip (guard[1]) is read. ---- */
+/* The schedule, one thread: state = {decay, warmup (0 or 1), updates} (doubles).  With t = state[2],
+ * beta = warmup ? min(decay, (1 + t) / (10 + t)) : decay in double; derived[0] = (float)(1.0 - beta), state[2] = t + 1.  guard[1] != 0:
+ * nothing changes, as hoig_adam_tick_guarded leaves its count.  HOIG_EINVAL: state or derived NULL. */
+int hoig_ema_tick(double *state, float *derived, const float *guard, hoig_stream_t stream);
+int hoig_ema_tick_host(double *state, float *derived, const float *guard);
+/* ema[i] = ema[i] + (param[i] - ema[i]) * derived[0] for i in [0, n), fp32, three roundings in that order (no contraction).  `param`
+ * is only read.  guard[1] != 0: the kernel returns before the first load.  HOIG_EINVAL, and nothing launched: a NULL ema, param or
+ * derived, n <= 0, ema or param not 16-byte aligned, the two ranges sharing an element (ema == param among them). */
+int hoig_ema_update(float *ema, const float *param, int64_t n, const float *derived, const float *guard, hoig_stream_t stream);
+int hoig_ema_update_host(float *ema, const float *param, int64_t n, const float *derived, const float *guard);
+/* Exchanges a[0 .. n) and b[0 .. n) in place.  HOIG_EINVAL, and nothing launched: a NULL pointer, n <= 0, a pointer not 16-byte
+ * aligned, overlapping ranges. */
+int hoig_swap_f32(float *a, float *b, int64_t n, hoig_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
