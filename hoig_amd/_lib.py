@@ -198,6 +198,17 @@ _SIGS = {
     'hoig_ema_update': [_vp, _vp, _i64, _vp, _vp, _vp],
     'hoig_ema_update_host': [_vp, _vp, _i64, _vp, _vp],
     'hoig_swap_f32': [_vp, _vp, _i64, _vp],
+    'hoig_daug_ws_floats': [_i],
+    'hoig_daug_tick': [_vp, _vp],
+    'hoig_daug_tick_host': [_vp],
+    'hoig_daug_draw': [_vp, _i, _i, _i, _i, _vp, _vp],
+    'hoig_daug_draw_host': [_vp, _i, _i, _i, _i, _vp],
+    'hoig_daug_adapt': [_vp, _vp, _i64, _vp],
+    'hoig_daug_adapt_host': [_vp, _vp, _i64],
+    'hoig_daug_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    'hoig_daug_fwd_host': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    'hoig_daug_bwd': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    'hoig_daug_bwd_host': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
 
@@ -262,6 +273,8 @@ def _load():
 
 lib = _load()
 
+DAUG_COLOR, DAUG_TRANSLATION, DAUG_CUTOUT = 1, 2, 4      # HOIG_DAUG_*: the bits of a record's flags and of the policy word
+DAUG_STATE_WORDS, DAUG_MAX_PARTS = 16, 16                # HOIG_DAUG_STATE_WORDS, HOIG_DAUG_MAX_PARTS
 GUARD_SKIP = 1                                   # HOIG_GUARD_SKIP
 GRAD_CHUNK = lib.hoig_grad_stats_chunk()         # HOIG_GRAD_CHUNK: elements of a stage-1 chunk of hoig_grad_stats
 GRAD_MAX_GRID = lib.hoig_grad_stats_max_grid()   # the most workgroups its stage 1 uses

@@ -25,6 +25,7 @@ import torch.distributed as dist
 from .. import _lib, ops
 from ..options import is_dexycb
 from ..ddp import FlatDDP
+from ..d_augment import SITE_G_FAKE as DAUG_SITE_G_FAKE, SITE_D_REAL as DAUG_SITE_D_REAL, SITE_D_FAKE as DAUG_SITE_D_FAKE
 from ..nn import FusedAdam
 from .base_model import BaseModel, strip_ddp_prefix
 from .networks import NetworksFactory
@@ -80,6 +81,7 @@ class Trainer(BaseModel):
     _sig = None
     _ema = None               # (class defaults: a model assembled without __init__, as bench.py's forward leg is, keeps no average)
     _eval_ema = False
+    _daug = None              # (likewise: no discriminator augmentation)
 
     def __init__(self, opt, use_ddp=False):
         super(Trainer, self).__init__(opt, use_ddp)
@@ -122,6 +124,11 @@ class Trainer(BaseModel):
         from ..ema import parse_options as parse_ema_options
         self._ema_decay, self._ema_warmup, self._eval_ema = parse_ema_options(opt, self._is_train)
         self._ema = None                 # EmaWeights of G; None with the option off, and in an eval-only model
+        # differentiable augmentation of everything D sees (docs/d_augment.md), off by default: opt.d_augment / HOIG_D_AUGMENT = a comma
+        # list out of 'color', 'translation', 'cutout'; opt.d_augment_p / HOIG_D_AUGMENT_P = a float in [0, 1] (1.0) or 'adaptive'
+        from ..d_augment import parse_options as parse_daug_options
+        self._daug_options = parse_daug_options(opt)
+        self._daug = None                # DAugment; None with the option off, and in an eval-only model
 
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
@@ -205,6 +212,13 @@ class Trainer(BaseModel):
         if self._ema_decay is not None:
             from ..ema import EmaWeights
             self._ema = EmaWeights(self._net(self._G), self._ema_decay, warmup=self._ema_warmup)
+        if self._daug_options is not None:
+            from ..d_augment import DAugment
+            if self._daug_options['adaptive'] and self._sync_active():
+                raise ValueError("d_augment_p 'adaptive' under an active gradient exchange: the ranks' p would drift apart "
+                                 '(give a fixed d_augment_p)')
+            rank = dist.get_rank() if (self._use_ddp and dist.is_initialized()) else 0
+            self._daug = DAugment(self.device, rank=rank, batch=getattr(self._opt, 'batch_size', None), **self._daug_options)
 
     def _init_prefetch_inputs(self):
         self._real_src = self._real_tsf = self._bg_mask = self._hand_mask = None
@@ -475,6 +489,14 @@ class Trainer(BaseModel):
     def _phase_g(self, keep_data_for_visuals=False, d_early=False):
         """Forward, the G loss and its backward (trainer.py:419-427).  Returns the fake target image and the event that marks the
         end of the forward (what the D step waits for)."""
+        if self._daug is not None:
+            # on the caller's stream, before any stream forks from it: the step index advances, and D(fake)'s records are drawn here
+            # too, before the D step of a 'd_early' iteration can move p beside them
+            b, h, w, _ = self._n['tsf_cond'].shape
+            if self._daug.batch is None:
+                self._daug.set_batch(b * self._world)
+            self._daug.tick()
+            self._daug.draw(DAUG_SITE_G_FAKE, b, h, w)
         _, _, fake_src_imgs, fake_tsf_imgs, fake_masks_bg, fake_masks_hand = \
             self.forward(keep_data_for_visuals=keep_data_for_visuals)
         ev_fwd = torch.cuda.Event()
@@ -696,14 +718,14 @@ class Trainer(BaseModel):
             with torch.cuda.stream(s_adv):
                 ops.test_delay('loss_adv')
                 self._wait_d()
-                d_fake = self._D.forward_nhwc(ops.cat_channels([fake_tsf, n['tsf_cond']]))
+                d_fake = self._D.forward_nhwc(self._d_fake_in(fake_tsf))
                 d_fake = ops.delay_backward(d_fake, 'loss_adv')
                 self._loss_g_adv = ops.lsgan_loss(d_fake, 0.0, o.lambda_D_prob, into=into('g_adv'))
             ops.cross_stream(fake_tsf, s_adv)
         else:
             s_vgg = None
             self._wait_d()
-            d_fake = self._D.forward_nhwc(ops.cat_channels([fake_tsf, n['tsf_cond']]))
+            d_fake = self._D.forward_nhwc(self._d_fake_in(fake_tsf))
             self._loss_g_adv = ops.lsgan_loss(d_fake, 0.0, o.lambda_D_prob, into=into('g_adv'))
         self._loss_g_rec = ops.l1_loss(fake_src, n['real_src'], o.lambda_rec, into=into('g_rec'))
         # the reference uses self._crt_tsf in both branches of `if use_vgg` (:443-446); it only exists with --use_vgg
@@ -721,6 +743,27 @@ class Trainer(BaseModel):
         self._loss_g_mask_smooth = T.value('g_mask_smooth')
         return T.total(self._loss_g_adv, self._loss_g_rec, *(tsf + masks + smooth))
 
+    def _d_fake_in(self, fake_tsf):
+        """D's input in the G loss: [fake | cond], under the records `_phase_g` drew for this step when D's inputs are augmented."""
+        cond = self._n['tsf_cond']
+        if self._daug is None:
+            return ops.cat_channels([fake_tsf, cond])
+        return ops.augment_cat(fake_tsf, cond, self._daug.params(DAUG_SITE_G_FAKE, fake_tsf.shape[0]))
+
+    def _d_both_in(self, fake_tsf):
+        """D's stacked input in the D loss: real over fake.  Augmented: both halves are written in place, each under its own draw, and
+        the real half is made every step instead of once per batch."""
+        n = self._n
+        if self._daug is None:
+            return torch.cat([n['d_real_in'], ops.cat_channels([fake_tsf, n['tsf_cond']])], dim=0)
+        nb, h, w, _ = fake_tsf.shape
+        cond = n['tsf_cond']
+        both = torch.empty((2 * nb, h, w, 3 + cond.shape[-1]), dtype=fake_tsf.dtype, device=fake_tsf.device)
+        with torch.no_grad():
+            ops.augment_cat(n['real_tsf'], cond, self._daug.draw(DAUG_SITE_D_REAL, nb, h, w), out=both[:nb])
+            ops.augment_cat(fake_tsf, cond, self._daug.draw(DAUG_SITE_D_FAKE, nb, h, w), out=both[nb:])
+        return both
+
     def _optimize_D(self, fake_tsf_imgs):
         """trainer.py:459-474."""
         o, n = self._opt, self._n
@@ -728,8 +771,10 @@ class Trainer(BaseModel):
         # the reference runs D twice (trainer.py:464-465); instance norm is per sample, so one stacked pass is identical
         nb = fake_tsf.shape[0]
         self._wait_d()
-        d_both = self._D.forward_nhwc(torch.cat([n['d_real_in'], ops.cat_channels([fake_tsf, n['tsf_cond']])], dim=0))
+        d_both = self._D.forward_nhwc(self._d_both_in(fake_tsf))
         d_real, d_fake = d_both[:nb], d_both[nb:]
+        if self._daug is not None and self._daug.adaptive:
+            self._daug.adapt(d_real.detach())
         T = self._d_terms
         T.begin()
         loss_real = ops.lsgan_loss(d_real, 1.0, o.lambda_D_prob, into=T.term('d'))
@@ -762,6 +807,11 @@ class Trainer(BaseModel):
             r = guard.report()
             out['grad_norm_' + tag], out['grad_max_' + tag] = r['norm'], r['max']
             out['skipped_' + tag], out['clipped_' + tag] = r['skipped'], r['clipped']
+        if self._daug is not None:                    # (likewise: DAugment.report() copies to the host)
+            r = self._daug.report()
+            out['d_aug_p'] = r['p']
+            if self._daug.adaptive:
+                out['d_aug_rt'] = r['rt']
         return out
 
     def grad_report(self):
@@ -859,6 +909,8 @@ class Trainer(BaseModel):
             sd = self._ema.state_dict(prefix='module.' if isinstance(self._G, FlatDDP) else '')      # (G's own keys)
             print('saved net: %s' % self._ckpt.write(sd, 'net', label, 'G_ema'))
             self._ckpt.write(dict(updates=self._ema.updates(), decay=self._ema.decay, warmup=self._ema.warmup), 'opt', label, 'G_ema')
+        if self._daug is not None:
+            self._ckpt.write(self._daug.state_dict(), 'opt', label, 'D_aug')
 
     def load(self):
         """HOIG_HOv3/models/trainer.py:562-575; the HOIG_DexYCB copy (its trainer.py:558-573) differs twice: it hands the file's
@@ -882,6 +934,21 @@ class Trainer(BaseModel):
                     self.update_learning_rate()
             if self._ema is not None:
                 self._load_ema(load_epoch)
+            if self._daug is not None:
+                self._load_daug(load_epoch)
+
+    def _load_daug(self, load_epoch):
+        quiet = dist.is_available() and dist.is_initialized() and dist.get_rank() != 0
+        path = self._ckpt.file('opt', load_epoch, 'D_aug')
+        if not os.path.isfile(path):
+            self._daug.reset()
+            if not quiet:
+                print('no augmentation checkpoint %s: step 0, p = %g' % (path, self._daug.p0))
+            return
+        sd = self._ckpt.read(path)
+        self._daug.load_state_dict(sd)
+        if not quiet:
+            print('loaded augmentation state: %s (step %d, p = %g)' % (path, sd['step'], sd['p']))
 
     def _load_ema(self, load_epoch):
         quiet = dist.is_available() and dist.is_initialized() and dist.get_rank() != 0

@@ -1175,7 +1175,7 @@ def _conv_dgrad_raw(d, g, w, dx, transposed=False, addend=None):
 def _reexport():
     import importlib
     g = globals()
-    for mod in ('ops_norm', 'ops_small', 'ops_attn', 'ops_loss'):
+    for mod in ('ops_norm', 'ops_small', 'ops_attn', 'ops_loss', 'ops_daug'):
         m = importlib.import_module('.' + mod, __package__)
         for k, v in vars(m).items():
             if not k.startswith('__') and k not in ('_o', 'L', 'ConvDesc', 'Function', 'torch', 'contextlib'):

@@ -913,6 +913,42 @@ int hoig_ema_update_host(float *ema, const float *param, int64_t n, const float 
  * aligned, overlapping ranges. */
 int hoig_swap_f32(float *a, float *b, int64_t n, hoig_stream_t stream);
 
+/* ---- DIFFERENTIABLE AUGMENTATION IN FRONT OF THE DISCRIMINATOR (hoig_amd/csrc/d_augment.hip, d_augment.h, d_augment_host.cpp;
+ *      hoig_amd/d_augment.py; docs/d_augment.md).  The *_host twins take host memory, make no HIP call and run the same inline
+ *      functions: their results are the device's, bit for bit.  Every entry point returns HOIG_EINVAL, and writes nothing, for a NULL
+ *      or misaligned pointer (state: 8 bytes; params: 16; floats: 4), a non-positive size or an unknown site. ---- */
+#define HOIG_DAUG_COLOR 1          /* the bits of a record's flags and of the state's policy word */
+#define HOIG_DAUG_TRANSLATION 2
+#define HOIG_DAUG_CUTOUT 4
+#define HOIG_DAUG_SITES 3          /* 0: D(fake) in the G phase, 1: real in the D phase, 2: fake in the D phase */
+#define HOIG_DAUG_STATE_WORDS 16   /* 64-bit words of the state (layout: d_augment.h, docs/d_augment.md) */
+#define HOIG_DAUG_THREADS 256      /* threads of a reduction workgroup */
+#define HOIG_DAUG_MAX_PARTS 16     /* the most partial sums per sample; ws holds B * HOIG_DAUG_MAX_PARTS floats */
+/* B * HOIG_DAUG_MAX_PARTS: the floats of the workspace hoig_daug_fwd / hoig_daug_bwd take (HOIG_EINVAL for B <= 0) */
+int hoig_daug_ws_floats(int B);
+/* One thread: the step index (state word 0) goes up by one.  Once per training step, before its first draw. */
+int hoig_daug_tick(uint64_t *state, hoig_stream_t stream);
+int hoig_daug_tick_host(uint64_t *state);
+/* params[i] = the 8-word record {b, s, k, ty, tx, cut_y0, cut_x0, flags} of sample i in [0, B) for maps of H x W, from
+ * Philox4x32-10 with key (seed, rank) and counters (step low, step high, site, 3 i + j), j = 0, 1, 2; a family that the policy lacks
+ * or whose gate fails writes its identity (b 0, s 1, k 1, shifts 0, box origin 0) and clears its flag. */
+int hoig_daug_draw(const uint64_t *state, int site, int B, int H, int W, uint32_t *params, hoig_stream_t stream);
+int hoig_daug_draw_host(const uint64_t *state, int site, int B, int H, int W, uint32_t *params);
+/* The adaptive probability: counts d_real[0 .. n) > 0 and < 0 (integers), adds them to the interval's counters, and on every
+ * `interval`-th call sets p <- clamp(p + sign((pos - neg) / total - target) * increment, 0, 1) and clears the counters. */
+int hoig_daug_adapt(uint64_t *state, const float *d_real, int64_t n, hoig_stream_t stream);
+int hoig_daug_adapt_host(uint64_t *state, const float *d_real, int64_t n);
+/* out [B][H][W][3 + k] = the augmented concatenation of img [B][H][W][3] and cond [B][H][W][k] under params [B][8] (NHWC fp32; `out`
+ * may be one half of a larger tensor).  Two launches: the per-sample image sums into ws (samples without the colour flag are left
+ * out), then the output.  With every flag clear `out` is hoig_cat2_channels' bit for bit.  `out` and `ws` may not overlap an input. */
+int hoig_daug_fwd(const float *img, const float *cond, const uint32_t *params, float *out, int B, int H, int W, int k, float *ws,
+                  hoig_stream_t stream);
+int hoig_daug_fwd_host(const float *img, const float *cond, const uint32_t *params, float *out, int B, int H, int W, int k, float *ws);
+/* dimg [B][H][W][3] = the gradient of hoig_daug_fwd with respect to img, from g [B][H][W][3 + k], the gradient of its output.  Two
+ * launches: the per-sample sums of g over the image channels of the surviving pixels into ws, then dimg. */
+int hoig_daug_bwd(const float *g, const uint32_t *params, float *dimg, int B, int H, int W, int k, float *ws, hoig_stream_t stream);
+int hoig_daug_bwd_host(const float *g, const uint32_t *params, float *dimg, int B, int H, int W, int k, float *ws);
+
 #ifdef __cplusplus
 }
 #endif
