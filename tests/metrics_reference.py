@@ -189,10 +189,18 @@ class LPIPSRef(object):
         fx, fy = self.fmaps((x.double() - mu) / sigma), self.fmaps((y.double() - mu) / sigma)
         val = 0
         for a, b, w in zip(fx, fy, self.heads):
-            na = a * torch.rsqrt((a ** 2).sum(1, keepdim=True) + 1e-10)
-            nb = b * torch.rsqrt((b ** 2).sum(1, keepdim=True) + 1e-10)
-            val = val + F.conv2d((na - nb) ** 2, w).mean(dim=(1, 2, 3))
+            val = val + lpips_layer(a.flatten(2).transpose(1, 2), b.flatten(2).transpose(1, 2), w.view(-1))
         return val
+
+
+def lpips_layer(fx, fy, w, dtype=torch.float64):
+    """(B,) distance of one layer: [B, HW, C] maps, (C,) weight, fp64.  Both maps are scaled to unit channel norm per pixel
+    (eps 1e-10 under the root), then mean over pixels of sum_c w_c (x_c - y_c)^2.  (dtype=torch.float32: the same statement in
+    fp32, for the floor of the number format.)"""
+    fx, fy, w = fx.to(dtype), fy.to(dtype), w.to(dtype).view(-1)
+    nx = fx * torch.rsqrt((fx ** 2).sum(-1, keepdim=True) + 1e-10)
+    ny = fy * torch.rsqrt((fy ** 2).sum(-1, keepdim=True) + 1e-10)
+    return (w * (nx - ny) ** 2).sum(-1).mean(-1)
 
 
 def lpips_given_batches(model, xs, ys, batch_size):
@@ -214,10 +222,21 @@ def _filter(x, g):
     return F.conv2d(x, g.view(1, 1, -1, 1).repeat(C, 1, 1, 1), groups=C)
 
 
-def ssim_level(X, Y, data_range, win=11, sigma=1.5, K=(0.01, 0.03)):
-    """(ssim, cs) per (image, channel), fp64."""
-    g = gauss_window(win, sigma)
-    X, Y = X.double(), Y.double()
+def ssim_pair(B, C, H, W, scale=1.0, seed=0):
+    """(X, Y) fp32 (B, C, H, W) in [0, scale]: a smooth map (5x5 average of rand) and its mix with fresh noise, the map's share
+    running from 0.2 to 0.9 across the batch, so that SSIM goes from far apart to close."""
+    g = torch.Generator().manual_seed(seed)
+    base = F.avg_pool2d(torch.rand(B, C, H, W, generator=g), 5, 1, 2)
+    other = torch.rand(B, C, H, W, generator=g)
+    mix = torch.linspace(0.2, 0.9, B).view(B, 1, 1, 1)
+    return base * scale, (mix * base + (1 - mix) * other) * scale
+
+
+def ssim_level(X, Y, data_range, win=11, sigma=1.5, K=(0.01, 0.03), dtype=torch.float64):
+    """(ssim, cs) per (image, channel), fp64 (dtype=torch.float32: the same statement in fp32, whose distance to fp64 is the floor
+    of the number format)."""
+    g = gauss_window(win, sigma).to(dtype)
+    X, Y = X.to(dtype), Y.to(dtype)
     C1, C2 = (K[0] * data_range) ** 2, (K[1] * data_range) ** 2
     m1, m2 = _filter(X, g), _filter(Y, g)
     s11, s22, s12 = _filter(X * X, g) - m1 ** 2, _filter(Y * Y, g) - m2 ** 2, _filter(X * Y, g) - m1 * m2

@@ -151,6 +151,68 @@ def test_lpips_path_value_is_mean_of_batch_means(tmp_path):
     assert abs(got - np.mean(per)) > 1e-6            # (not the mean over images)
 
 
+def test_ssim_level_equals_a_literal_loop_over_windows():
+    X, Y = R.ssim_pair(1, 2, 13, 12, 1.0, 5)
+    X, Y = X.double(), Y.double()
+    win, C1, C2 = 3, 0.01 ** 2, 0.03 ** 2
+    g = R.gauss_window(win, 1.5)
+    g2 = g.view(-1, 1) * g.view(1, -1)
+    s, cs = R.ssim_level(X, Y, 1.0, win)
+    assert s.shape == (1, 2) and cs.shape == (1, 2)
+    for c in range(2):
+        sv, cv = [], []
+        for i in range(13 - win + 1):
+            for j in range(12 - win + 1):
+                a, b = X[0, c, i:i + win, j:j + win], Y[0, c, i:i + win, j:j + win]
+                ma, mb = (g2 * a).sum(), (g2 * b).sum()
+                va, vb, vab = (g2 * a * a).sum() - ma * ma, (g2 * b * b).sum() - mb * mb, (g2 * a * b).sum() - ma * mb
+                cv.append((2 * vab + C2) / (va + vb + C2))
+                sv.append((2 * ma * mb + C1) / (ma * ma + mb * mb + C1) * cv[-1])
+        assert len(sv) == 11 * 10
+        assert abs(torch.stack(sv).mean().item() - s[0, c].item()) < 1e-12
+        assert abs(torch.stack(cv).mean().item() - cs[0, c].item()) < 1e-12
+
+
+def test_ssim_pair_spans_far_to_close():
+    X, Y = R.ssim_pair(3, 2, 27, 75, 255.0, 1)
+    assert X.dtype == torch.float32 and X.shape == Y.shape == (3, 2, 27, 75)
+    assert 0 <= X.min() and X.max() <= 255 and 0 <= Y.min() and Y.max() <= 255 and X.max() > 100
+    s = R.ssim_level(X, Y, 255.0)[0].mean(1)
+    assert s[0] < s[1] < s[2] and s[0] < 0.1 and s[2] > 0.5, s
+
+
+def test_lpips_layer_reference():
+    g = torch.Generator().manual_seed(0)
+    fx = torch.relu(torch.randn(3, 37, 20, generator=g, dtype=torch.float64))
+    fy = torch.relu(torch.randn(3, 37, 20, generator=g, dtype=torch.float64))
+    w = torch.rand(20, generator=g, dtype=torch.float64)
+    v = R.lpips_layer(fx, fy, w)
+    assert v.shape == (3,) and v.min() > 0
+    assert torch.equal(v, R.lpips_layer(fy, fx, w))                     # symmetric
+    assert torch.equal(R.lpips_layer(fx, fx, w), torch.zeros(3, dtype=torch.float64))
+    # a literal loop over pixels and channels
+    want = 0.0
+    for p in range(37):
+        nx, ny = (fx[1, p] ** 2).sum() + 1e-10, (fy[1, p] ** 2).sum() + 1e-10
+        want += sum(w[c] * (fx[1, p, c] / nx.sqrt() - fy[1, p, c] / ny.sqrt()) ** 2 for c in range(20))
+    assert abs(want.item() / 37 - v[1].item()) < 1e-12
+
+
+def test_lpips_per_image_keeps_its_value():
+    """per_image now goes through lpips_layer: the value it had as a 1x1 convolution of the squared difference of NCHW maps."""
+    ref = R.LPIPSRef(R.alexnet_state_dict(1), R.lpips_state_dict(2))
+    g = torch.Generator().manual_seed(1)
+    x, y = torch.randn(2, 3, 67, 75, generator=g), torch.randn(2, 3, 67, 75, generator=g)
+    mu, sigma = torch.tensor(R.LPIPS_MU).double().view(1, 3, 1, 1), torch.tensor(R.LPIPS_SIGMA).double().view(1, 3, 1, 1)
+    old = 0
+    for a, b, w in zip(ref.fmaps((x.double() - mu) / sigma), ref.fmaps((y.double() - mu) / sigma), ref.heads):
+        na = a * torch.rsqrt((a ** 2).sum(1, keepdim=True) + 1e-10)
+        nb = b * torch.rsqrt((b ** 2).sum(1, keepdim=True) + 1e-10)
+        old = old + F.conv2d((na - nb) ** 2, w).mean(dim=(1, 2, 3))
+    got = ref.per_image(x, y)
+    assert old.min() > 0.01 and (got - old).abs().max().item() < 1e-12
+
+
 def test_cli_validates_arguments(tmp_path):
     R.write_pngs(str(tmp_path / 'a'), 1, 16, 0)
     with pytest.raises(SystemExit):
