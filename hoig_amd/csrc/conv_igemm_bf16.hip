@@ -276,9 +276,11 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_bf16_kernel(const Args p) 
 __device__ __forceinline__ void split_weight(float x, bool f16, unsigned short &h, unsigned short &l) {
     if (f16) {
         const float xs = x * W_SCALE_F16;
-        const _Float16 hh = (_Float16)xs;
+        // (the compiler folds product and conversion into one fma(x, 256, +0) -> fp16, which turns x = -0 into +0: hi takes the sign
+        //  of x back -- every other result has it already -- so that hi is fp16(256 x) to the bit and lo = +0 for either zero)
+        h = __builtin_bit_cast(unsigned short, (_Float16)xs) | (unsigned short)((__float_as_uint(x) >> 16) & 0x8000u);
+        const _Float16 hh = __builtin_bit_cast(_Float16, h);
         const _Float16 ll = (_Float16)(xs - (float)hh);
-        h = __builtin_bit_cast(unsigned short, hh);
         l = __builtin_bit_cast(unsigned short, ll);
     } else {
         h = hoig_f2bf(x);

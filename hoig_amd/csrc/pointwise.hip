@@ -447,8 +447,8 @@ __global__ void maxpool_bwd_kernel(const float *__restrict__ x, const float *__r
 //   m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g; denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m/denom
 __global__ __launch_bounds__(NT) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                   float *__restrict__ v, int64_t n, float step_size, float omb1, float b2,
-                                                  float omb2, float eps, float bc2_sqrt, float gscale) {
-    const int64_t n4 = n >> 2;
+                                                  float omb2, float eps, float bc2_sqrt, float gscale, bool vec) {
+    const int64_t n4 = vec ? n >> 2 : 0;          // (a pointer off a 16-byte boundary: the scalar loop below takes all n)
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NT) {
         float4 pp = reinterpret_cast<float4 *>(p)[i];
         const float4 gg = reinterpret_cast<const float4 *>(g)[i];
@@ -505,14 +505,14 @@ __global__ void adam_tick_kernel(double *__restrict__ state, float *__restrict__
 template <bool GUARD>
 __global__ __launch_bounds__(NT) void adam_dev_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                       float *__restrict__ v, int64_t n, const float *__restrict__ derived,
-                                                      float gscale, const float *__restrict__ guard) {
+                                                      float gscale, const float *__restrict__ guard, bool vec) {
     if constexpr (GUARD) {
         if (guard[1] != 0.f) return;
         gscale = gscale * guard[0];
     }
     const float step_size = derived[0], omb1 = derived[1], b2 = derived[2], omb2 = derived[3], eps = derived[4],
                 bc2_sqrt = derived[5];
-    const int64_t n4 = n >> 2;
+    const int64_t n4 = vec ? n >> 2 : 0;          // (as adam_kernel)
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NT) {
         float4 pp = reinterpret_cast<float4 *>(p)[i];
         const float4 gg = reinterpret_cast<const float4 *>(g)[i];
@@ -684,6 +684,11 @@ extern "C" int hoig_compose_bwd(const float *bg, const float *obj, const float *
 static bool loss_vec_ok(const void *a, const void *b, const void *c) {
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
+// the Adam slice entry points are called at any element of the flat buffers (FusedAdam.step(ready=...)): float4 accesses only when
+// all four pointers sit on 16-byte boundaries, the scalar loop for every element otherwise
+static bool adam_vec_ok(const void *p, const void *g, const void *m, const void *v) {
+    return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+}
 extern "C" int hoig_loss_fwd_bwd(int kind, const float *pred, const float *target, float target_const, float gscale,
                                  float *out, float *dpred, int64_t n, hoig_stream_t stream) {
     if (!pred || !out || kind < 0 || kind > 2) return HOIG_EINVAL;
@@ -760,7 +765,8 @@ extern "C" int hoig_adam_step(float *param, const float *grad, float *exp_avg, f
     // 1-beta evaluated in double like torch does (python floats), then rounded once
     adam_kernel<<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, step_size,
                                                                (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                                                               (float)eps, bc2_sqrt, grad_scale);
+                                                               (float)eps, bc2_sqrt, grad_scale,
+                                                               adam_vec_ok(param, grad, exp_avg, exp_avg_sq));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }
@@ -773,7 +779,8 @@ extern "C" int hoig_adam_tick(double *state, float *derived, hoig_stream_t strea
 extern "C" int hoig_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                   const float *derived, float grad_scale, hoig_stream_t stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !derived) return HOIG_EINVAL;
-    adam_dev_kernel<false><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, nullptr);
+    adam_dev_kernel<false><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, nullptr,
+                                                                           adam_vec_ok(param, grad, exp_avg, exp_avg_sq));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }
@@ -786,7 +793,8 @@ extern "C" int hoig_adam_tick_guarded(double *state, float *derived, const float
 extern "C" int hoig_adam_step_dev_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                           const float *derived, float grad_scale, const float *guard, hoig_stream_t stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !derived || !guard) return HOIG_EINVAL;
-    adam_dev_kernel<true><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, guard);
+    adam_dev_kernel<true><<<hoig_stream_grid(n / 4 + 1, NT), NT, 0, ST>>>(param, grad, exp_avg, exp_avg_sq, n, derived, grad_scale, guard,
+                                                                          adam_vec_ok(param, grad, exp_avg, exp_avg_sq));
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;
 }

@@ -152,8 +152,9 @@ int hoig_conv2d_fwd_heads(const hoig_conv_desc *d, const float *x, const float *
  * fp16(256*w - hi) -- forward launches split their operands on fp16 and scale the accumulator by 1/256 -- the
  * DATA-GRADIENT planes (for_dgrad=1) hold bf16(w) and bf16(w - hi).  for_dgrad=0: n = co, k = (r*S+s)*Ci + ci
  * (forward GEMM); for_dgrad=1: n = ci, k = (r*S+s)*Co + co (data-gradient GEMM).  A plane is stored in 32(n) x 32(k)
- * blocks of 2 KB: element (n, k) at ((n/32)*(K/32) + k/32)*1024 + (n%32)*32 + k%32, so that the weight tile of one
- * k-step is a few fully used contiguous runs.  Co and Ci must be multiples of 32 (else HOIG_EUNSUPPORTED).  The *_packed
+ * blocks of 2 KB, and inside a block the four 8-element groups of a row are XOR-swizzled by the row: element (n, k) at
+ * ((n/32)*(K/32) + k/32)*1024 + (n%32)*32 + ((((k%32)/8) ^ ((n/4)%4))*8) + k%8 (plane_index, hoig_amd/csrc/conv_bf16_common.h: the
+ * block is the LDS image the kernels read), so that the weight tile of one k-step is a few fully used contiguous runs.  Co and Ci must be multiples of 32 (else HOIG_EUNSUPPORTED).  The *_packed
  * entry points return HOIG_EUNSUPPORTED for shapes outside the fast path (channels % 32 != 0, <= 32 output channels);
  * use the fp32 entry points then. */
 int hoig_pack_conv_weight_bf16(const float *w, int Co, int RS, int Ci, int for_dgrad, uint16_t *hi, uint16_t *lo /*nullable*/,
@@ -426,7 +427,10 @@ int hoig_sum(const float *x, float *out, int64_t n, hoig_stream_t stream);
 int hoig_sum_scaled(const float *x, float scale, float *out, int64_t n, hoig_stream_t stream);
 
 /* ---- fused Adam over one flat parameter buffer (torch.optim.Adam defaults of trainer.py:275-278:
- *      no weight decay, no amsgrad): step is the 1-based step count after increment ---- */
+ *      no weight decay, no amsgrad): step is the 1-based step count after increment ----
+ * hoig_adam_step, hoig_adam_step_dev and hoig_adam_step_dev_guarded take a slice that may start at ANY element: when one of the four
+ * pointers is not 16-byte aligned the kernel takes its scalar loop for all n (the same arithmetic, element for element; slower), so
+ * a slice cut off a multiple of 4 elements is as valid as an aligned one. */
 int hoig_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, double lr,
                    double beta1, double beta2, double eps, int step, float grad_scale, hoig_stream_t stream);
 
