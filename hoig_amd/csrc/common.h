@@ -29,6 +29,25 @@ struct hoig_once {
     void set() { mask.fetch_or(1ull << dev(), std::memory_order_release); }
 };
 
+// One launch: Kernel<<<grid, block, lds, st>>>(args...) and its check.  A kernel that needs more than the default 64 KB of dynamic LDS
+// names its opt-in LDS_OPT_IN (bytes, a compile-time constant); it is set on that kernel's first launch on each device, from one flag
+// per instantiation -- per kernel -- so the kernel launched and the kernel opted in cannot differ.
+template <auto Kernel, int LDS_OPT_IN = 0, class... A>
+int hoig_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    if constexpr (LDS_OPT_IN > 0) {
+        static hoig_once once;
+        if (!once.done()) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_OPT_IN) !=
+                hipSuccess)
+                return HOIG_ELAUNCH;
+            once.set();
+        }
+    }
+    Kernel<<<grid, block, lds, st>>>(args...);
+    HOIG_LAUNCH_CHECK();
+    return HOIG_OK;
+}
+
 static inline int64_t hoig_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Launchers that one .hip file defines and another calls (the dispatchers of conv_igemm.hip walk them in turn): each takes the layers it

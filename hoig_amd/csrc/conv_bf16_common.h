@@ -16,6 +16,12 @@ namespace hoig_detail {
         else if ((ns) == 3) { constexpr int NSX = 3; __VA_ARGS__; }            \
         else { constexpr int NSX = 1; __VA_ARGS__; }                           \
     } while (0)
+// the forward's fp16-split operands against the data gradient's bf16 ones: a launcher's runtime `f16` as the kernels' F16 template value
+#define HOIG_F16_SWITCH(flag, ...)                                             \
+    do {                                                                       \
+        if (flag) { constexpr bool F16X = true; __VA_ARGS__; }                 \
+        else { constexpr bool F16X = false; __VA_ARGS__; }                     \
+    } while (0)
 __host__ __device__ constexpr int ns_a(int nsx) { return nsx == 1 ? 1 : 2; }
 __host__ __device__ constexpr int ns_b(int nsx) { return nsx == 2 ? 2 : 1; }
 inline int ns_of_precision(int precision) {

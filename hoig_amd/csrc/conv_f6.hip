@@ -537,44 +537,21 @@ static int launch_f6(const hoig_conv_desc *d, const float *x, const float *x2, i
     a.nblk_n = a.N / (n64 ? 64 : 128);
     a.nblk = ptiles * a.nblk_n;
     if (a.nblk < g_f6_min_tiles) return HOIG_EUNSUPPORTED;
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_f6_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                BTile<128>::SMEM) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_f6_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                BTile<64>::SMEM) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
+    constexpr int S64 = BTile<64>::SMEM, S128 = BTile<128>::SMEM, S64N = S64 + NORMIN_BYTES, S128N = S128 + NORMIN_BYTES;
     if (in_scale) {
-        static hoig_once once_n;
-        if (!once_n.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_f6_kernel<128, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    BTile<128>::SMEM + NORMIN_BYTES) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_f6_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    BTile<64>::SMEM + NORMIN_BYTES) != hipSuccess)
-                return HOIG_ELAUNCH;
-            once_n.set();
-        }
         if (n64) {
             HOIG_ROUTE_F(f6_64_normin);
-            conv_halo3_f6_kernel<64, true><<<a.nblk, NT, BTile<64>::SMEM + NORMIN_BYTES, st>>>(a);
-        } else {
-            HOIG_ROUTE_F(f6_128_normin);
-            conv_halo3_f6_kernel<128, true><<<a.nblk, NT, BTile<128>::SMEM + NORMIN_BYTES, st>>>(a);
+            return hoig_launch<conv_halo3_f6_kernel<64, true>, S64N>(a.nblk, NT, S64N, st, a);
         }
-        HOIG_LAUNCH_CHECK();
-        return HOIG_OK;
+        HOIG_ROUTE_F(f6_128_normin);
+        return hoig_launch<conv_halo3_f6_kernel<128, true>, S128N>(a.nblk, NT, S128N, st, a);
     }
     if (n64) {
         HOIG_ROUTE_F(f6_64);
-        conv_halo3_f6_kernel<64><<<a.nblk, NT, BTile<64>::SMEM, st>>>(a);
-    } else {
-        HOIG_ROUTE_F(f6_128);
-        conv_halo3_f6_kernel<128><<<a.nblk, NT, BTile<128>::SMEM, st>>>(a);
+        return hoig_launch<conv_halo3_f6_kernel<64>, S64>(a.nblk, NT, S64, st, a);
     }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_ROUTE_F(f6_128);
+    return hoig_launch<conv_halo3_f6_kernel<128>, S128>(a.nblk, NT, S128, st, a);
 }
 
 // forward 3x3 stride-1 pad-1 convolution; HOIG_EUNSUPPORTED for every shape outside this kernel's tiling (the caller then uses

@@ -332,38 +332,15 @@ __global__ __launch_bounds__(512) void conv_flat_m16_kernel(const FlatArgs p) {
 
 template <int NSX, int KS, bool F16, bool SPLITK>
 int launch_one(const FlatArgs &a, dim3 grid, size_t shm, hipStream_t st) {
-    if (hoig_tuning(HOIG_TUNE_WDMA16) >= 2) {              // (2: the flattened-axis kernel too)
-        static hoig_once once_d;
-        if (!once_d.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flat_m16_kernel<NSX, KS, F16, SPLITK, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return HOIG_ELAUNCH;
-            once_d.set();
-        }
-        conv_flat_m16_kernel<NSX, KS, F16, SPLITK, true><<<grid, 512, shm, st>>>(a);
-        HOIG_LAUNCH_CHECK();
-        return HOIG_OK;
-    }
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flat_m16_kernel<NSX, KS, F16, SPLITK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
-    conv_flat_m16_kernel<NSX, KS, F16, SPLITK><<<grid, 512, shm, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (hoig_tuning(HOIG_TUNE_WDMA16) >= 2)                // (2: the flattened-axis kernel too)
+        return hoig_launch<conv_flat_m16_kernel<NSX, KS, F16, SPLITK, true>, 160 * 1024>(grid, 512, shm, st, a);
+    return hoig_launch<conv_flat_m16_kernel<NSX, KS, F16, SPLITK>, 160 * 1024>(grid, 512, shm, st, a);
 }
 
 template <int KS>
 int launch_ks(const FlatArgs &a, int ns, dim3 grid, size_t shm, bool split, hipStream_t st) {
-    if (split) {
-        if (a.f16) HOIG_NS_SWITCH(ns, return launch_one<NSX, KS, true, true>(a, grid, shm, st));
-        else HOIG_NS_SWITCH(ns, return launch_one<NSX, KS, false, true>(a, grid, shm, st));
-    }
-    if (a.f16) HOIG_NS_SWITCH(ns, return launch_one<NSX, KS, true, false>(a, grid, shm, st));
-    else HOIG_NS_SWITCH(ns, return launch_one<NSX, KS, false, false>(a, grid, shm, st));
+    if (split) HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_one<NSX, KS, F16X, true>(a, grid, shm, st)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_one<NSX, KS, F16X, false>(a, grid, shm, st)));
     return HOIG_EINVAL;
 }
 

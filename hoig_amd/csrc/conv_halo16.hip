@@ -660,16 +660,9 @@ __global__ __launch_bounds__(256) void conv_halo_s2_m16_kernel(const HaloArgs p)
 template <int NS, int BN>
 int launch_one(const HaloArgs &a, hipStream_t st) {
     constexpr int WM = 4, WN = 2;
-    constexpr size_t shm = M16Layout<WM, BN>::bytes(NS);
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
+    constexpr int shm = (int)M16Layout<WM, BN>::bytes(NS);
+    const dim3 grid(a.nblk), block(64 * WM * WN);
+    const bool wdma = hoig_tuning(HOIG_TUNE_WDMA16) != 0 && a.N % BN == 0;       // weight tiles by LDS-DMA (whole channel tiles only)
     if (a.a_split) {                                       // pre-split gathered tensor: bf16 data-gradient launches without x split
         if (a.in_scale) return HOIG_EUNSUPPORTED;
         if constexpr (NS == 2) return HOIG_EUNSUPPORTED;
@@ -677,64 +670,21 @@ int launch_one(const HaloArgs &a, hipStream_t st) {
             if (a.f16 || a.A2) return HOIG_EUNSUPPORTED;
             if (a.b_split > 0) BN == 64 ? HOIG_ROUTE_D(halo3_m16_64_split_pair) : HOIG_ROUTE_D(halo3_m16_128_split_pair);
             else BN == 64 ? HOIG_ROUTE_D(halo3_m16_64_split) : HOIG_ROUTE_D(halo3_m16_128_split);
-            static hoig_once once_s;
-            if (!once_s.done()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-                    return HOIG_ELAUNCH;
-                once_s.set();
-            }
-            if (hoig_tuning(HOIG_TUNE_WDMA16) != 0 && a.N % BN == 0) {
-                static hoig_once once_sd;
-                if (!once_sd.done()) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, false, true, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-                        return HOIG_ELAUNCH;
-                    once_sd.set();
-                }
-                conv_halo3_m16_kernel<NS, WM, WN, BN, false, true, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-            } else
-                conv_halo3_m16_kernel<NS, WM, WN, BN, false, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-            HOIG_LAUNCH_CHECK();
-            return HOIG_OK;
+            if (wdma) return hoig_launch<conv_halo3_m16_kernel<NS, WM, WN, BN, false, true, true>, shm>(grid, block, shm, st, a);
+            return hoig_launch<conv_halo3_m16_kernel<NS, WM, WN, BN, false, true>, shm>(grid, block, shm, st, a);
         }
     }
     if (a.in_scale) {                                      // inference chain: norm + ReLU of the gathered tensor applied in the loader
         if (!a.f16 || a.N % BN || !a.in_shift || a.b_split > 0) return HOIG_EUNSUPPORTED;
         BN == 64 ? HOIG_ROUTE_F(halo3_m16_64_normin) : HOIG_ROUTE_F(halo3_m16_128_normin);
-        static hoig_once once_n;
-        if (!once_n.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-                return HOIG_ELAUNCH;
-            once_n.set();
-        }
-        conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-        HOIG_LAUNCH_CHECK();
-        return HOIG_OK;
+        return hoig_launch<conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true, true>, shm>(grid, block, shm, st, a);
     }
     if (a.b_split > 0 && a.f16) BN == 64 ? HOIG_ROUTE_F(halo3_m16_64_pair) : HOIG_ROUTE_F(halo3_m16_128_pair);
     else if (BN == 64) HOIG_ROUTE_FD(a.f16, halo3_m16_64);
     else HOIG_ROUTE_FD(a.f16, halo3_m16_128);
-    if (hoig_tuning(HOIG_TUNE_WDMA16) != 0 && a.N % BN == 0) {       // weight tiles by LDS-DMA (whole channel tiles only)
-        static hoig_once once_d;
-        if (!once_d.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_m16_kernel<NS, WM, WN, BN, false, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-                return HOIG_ELAUNCH;
-            once_d.set();
-        }
-        if (a.f16) conv_halo3_m16_kernel<NS, WM, WN, BN, true, false, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-        else conv_halo3_m16_kernel<NS, WM, WN, BN, false, false, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-        HOIG_LAUNCH_CHECK();
-        return HOIG_OK;
-    }
-    if (a.f16) conv_halo3_m16_kernel<NS, WM, WN, BN, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-    else conv_halo3_m16_kernel<NS, WM, WN, BN, false><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_F16_SWITCH(a.f16,
+                    if (wdma) return hoig_launch<conv_halo3_m16_kernel<NS, WM, WN, BN, F16X, false, true>, shm>(grid, block, shm, st, a);
+                    return hoig_launch<conv_halo3_m16_kernel<NS, WM, WN, BN, F16X>, shm>(grid, block, shm, st, a));
 }
 
 template <bool SCATTER>
@@ -755,15 +705,9 @@ int launch_s2(const HaloArgs &a, int ns, hipStream_t st) {
     if (pipe == 2 || (pipe != 0 && a.nblk <= 256)) return launch_halo_s2_m16p(a, ns, SCATTER, false, st);
     if (n64) SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_m16_64) : HOIG_ROUTE_FD(a.f16, s2g_m16_64);
     else SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_m16_128) : HOIG_ROUTE_FD(a.f16, s2g_m16_128);
-    if (n64) {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 64, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 64, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));
-    } else {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 128, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_s2_m16_kernel<NSX, 128, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));
-    }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (n64)
+        HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_s2_m16_kernel<NSX, 64, SCATTER, F16X>>(a.nblk, 256, 0, st, a)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_s2_m16_kernel<NSX, 128, SCATTER, F16X>>(a.nblk, 256, 0, st, a)));
 }
 
 }  // namespace

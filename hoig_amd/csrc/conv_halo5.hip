@@ -281,20 +281,11 @@ __global__ __launch_bounds__(NT) void conv_halo5_m16_kernel(const FlatArgs p) {
 template <int NSX, bool F16, bool SPLITK>
 int launch_one(const FlatArgs &a, dim3 grid, hipStream_t st) {
     constexpr int TPS = taps_per_step(NSX);
-    constexpr size_t shm = lds_bytes(NSX, TPS);
+    constexpr int shm = (int)lds_bytes(NSX, TPS);
     static_assert(shm <= 160 * 1024, "the halo and the weight buffers must fit in LDS");
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo5_m16_kernel<NSX, F16, SPLITK, TPS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     if (SPLITK) HOIG_ROUTE_FD(F16, halo5_m16_ksplit);
     else HOIG_ROUTE_FD(F16, halo5_m16);
-    conv_halo5_m16_kernel<NSX, F16, SPLITK, TPS><<<grid, NT, shm, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<conv_halo5_m16_kernel<NSX, F16, SPLITK, TPS>, shm>(grid, NT, shm, st, a);
 }
 
 }  // namespace
@@ -324,12 +315,8 @@ int launch_halo5_m16(FlatArgs a, int ns, hipStream_t st) {
     split = (int)hoig_cdiv(steps, a.steps_per_split);
     dim3 grid(a.nblk, split);
     if (split > 1 && hipMemsetAsync(a.C, 0, (size_t)a.Bn * a.Hd * a.Wd * a.N * sizeof(float), st) != hipSuccess) return HOIG_ELAUNCH;
-    if (split > 1) {
-        if (a.f16) HOIG_NS_SWITCH(ns, return launch_one<NSX, true, true>(a, grid, st));
-        else HOIG_NS_SWITCH(ns, return launch_one<NSX, false, true>(a, grid, st));
-    }
-    if (a.f16) HOIG_NS_SWITCH(ns, return launch_one<NSX, true, false>(a, grid, st));
-    else HOIG_NS_SWITCH(ns, return launch_one<NSX, false, false>(a, grid, st));
+    if (split > 1) HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_one<NSX, F16X, true>(a, grid, st)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_one<NSX, F16X, false>(a, grid, st)));
     return HOIG_EINVAL;
 }
 

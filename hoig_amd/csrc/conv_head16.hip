@@ -182,20 +182,12 @@ template <int CO, int KSTEPS>
 int launch_head7(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y, unsigned long long acts,
                  hipStream_t st) {
     constexpr int NFRAG = H7 * KSTEPS * h7_nt(CO);
-    constexpr size_t lds = (size_t)NFRAG * 2 * 64 * 16 + (size_t)2 * (H7_MAXT * 16 + 6) * h7_zs(CO) * 4;
+    constexpr int lds = NFRAG * 2 * 64 * 16 + 2 * (H7_MAXT * 16 + 6) * h7_zs(CO) * 4;
     static_assert(lds <= 160 * 1024, "LDS");
-    static hoig_once attr;
-    if (!attr.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv_head7_m16_kernel<CO, KSTEPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return HOIG_ELAUNCH;
-        attr.set();
-    }
     const int n_strips = (d->Wi + H7_OUTW - 1) / H7_OUTW, n_chunks = (d->Hi + H7_TH - 1) / H7_TH;
     HOIG_ROUTE_F(head7);
-    conv_head7_m16_kernel<CO, KSTEPS><<<d->B * n_chunks * n_strips, H7_THREADS, lds, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, acts, d->slope,
-                                                                                   n_strips, n_chunks);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<conv_head7_m16_kernel<CO, KSTEPS>, lds>(d->B * n_chunks * n_strips, H7_THREADS, lds, st, x, w, bias, y, d->B, d->Hi,
+                                                               d->Wi, acts, d->slope, n_strips, n_chunks);
 }
 
 }  // namespace

@@ -539,14 +539,11 @@ int launch_igemm(IgemmArgs a, bool ncontig, hipStream_t st) {
     else if (BM == 128) HOIG_ROUTE_FD(!ncontig, igemm_f32_128x128);
     else HOIG_ROUTE_FD(!ncontig, igemm_f32_64x128);
     if (vec) {
-        if (ncontig) igemm_f32_kernel<BM, BN, WM, WN, 4, true><<<grid, block, 0, st>>>(a);
-        else igemm_f32_kernel<BM, BN, WM, WN, 4, false><<<grid, block, 0, st>>>(a);
-    } else {
-        if (ncontig) igemm_f32_kernel<BM, BN, WM, WN, 1, true><<<grid, block, 0, st>>>(a);
-        else igemm_f32_kernel<BM, BN, WM, WN, 1, false><<<grid, block, 0, st>>>(a);
+        if (ncontig) return hoig_launch<igemm_f32_kernel<BM, BN, WM, WN, 4, true>>(grid, block, 0, st, a);
+        return hoig_launch<igemm_f32_kernel<BM, BN, WM, WN, 4, false>>(grid, block, 0, st, a);
     }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (ncontig) return hoig_launch<igemm_f32_kernel<BM, BN, WM, WN, 1, true>>(grid, block, 0, st, a);
+    return hoig_launch<igemm_f32_kernel<BM, BN, WM, WN, 1, false>>(grid, block, 0, st, a);
 }
 
 int dispatch_igemm(IgemmArgs a, bool ncontig, hipStream_t st) {

@@ -281,15 +281,9 @@ int launch(Args a, int ns, hipStream_t st) {
     else if (BN == 128) HOIG_ROUTE_FD(a.f16, igemm_m16_64x128);
     else if (BM == 128) HOIG_ROUTE_FD(a.f16, igemm_m16_128x64);
     else HOIG_ROUTE_FD(a.f16, igemm_m16_64x64);
-    if (a.ksplit > 1) {
-        if (a.f16) HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, true, true><<<grid, NT, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, false, true><<<grid, NT, 0, st>>>(a));
-    } else {
-        if (a.f16) HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, true, false><<<grid, NT, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, igemm_m16_kernel<BM, BN, WM, WN, NSX, false, false><<<grid, NT, 0, st>>>(a));
-    }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (a.ksplit > 1)
+        HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<igemm_m16_kernel<BM, BN, WM, WN, NSX, F16X, true>>(grid, NT, 0, st, a)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<igemm_m16_kernel<BM, BN, WM, WN, NSX, F16X, false>>(grid, NT, 0, st, a)));
 }
 
 }  // namespace

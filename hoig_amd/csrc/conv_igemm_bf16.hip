@@ -496,10 +496,7 @@ int launch(Args a, int ns, hipStream_t st) {
     else if (BN == 128) HOIG_ROUTE_FD(a.f16, igemm_bf16_64x128);
     else if (BM == 128) HOIG_ROUTE_FD(a.f16, igemm_bf16_128x64);
     else HOIG_ROUTE_FD(a.f16, igemm_bf16_64x64);
-    if (a.f16) HOIG_NS_SWITCH(ns, igemm_bf16_kernel<BM, BN, WM, WN, NSX, BK, true><<<grid, NT, 0, st>>>(a));
-    else HOIG_NS_SWITCH(ns, igemm_bf16_kernel<BM, BN, WM, WN, NSX, BK, false><<<grid, NT, 0, st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<igemm_bf16_kernel<BM, BN, WM, WN, NSX, BK, F16X>>(grid, NT, 0, st, a)));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1022,23 +1019,11 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_halo3_bf16_kernel(const Hal
 template <int NS, int WM, int WN, int BN, int MODE>
 int launch_halo3_one(const HaloArgs &a, hipStream_t st) {
     constexpr int HPIX = (2 * WM + 2) * 34;
-    constexpr size_t shm = (MODE == 1 ? 2 : 1) * (ns_a(NS) * (HPIX * 80)) + (MODE == 0 ? 1 : 2) * (3 * ns_b(NS) * (BN * 64));
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
+    constexpr int shm = (MODE == 1 ? 2 : 1) * (ns_a(NS) * (HPIX * 80)) + (MODE == 0 ? 1 : 2) * (3 * ns_b(NS) * (BN * 64));
     if (BN == 64) HOIG_ROUTE_FD(a.f16, halo3_64);
     else if (MODE == 1) HOIG_ROUTE_FD(a.f16, halo3_128w);
     else HOIG_ROUTE_FD(a.f16, halo3_128);
-    if (a.f16) conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, true><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-    else conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, false><<<a.nblk, 64 * WM * WN, shm, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo3_bf16_kernel<NS, WM, WN, BN, MODE, F16X>, shm>(a.nblk, 64 * WM * WN, shm, st, a));
 }
 
 
@@ -1385,15 +1370,10 @@ int launch_halo_s2(HaloArgs a, int ns, hipStream_t st) {
     if (hoig_tuning(HOIG_TUNE_S2_16) != 0 && !(SCATTER && n64 && ns == 2)) return launch_halo_s2_m16(a, ns, SCATTER, st);
     if (n64) SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_64) : HOIG_ROUTE_FD(a.f16, s2g_64);
     else SCATTER ? HOIG_ROUTE_FD(a.f16, s2s_128) : HOIG_ROUTE_FD(a.f16, s2g_128);
-    if (n64) {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 64, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 64, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));
-    } else {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 128, SCATTER, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_s2_bf16_kernel<NSX, 128, SCATTER, false><<<a.nblk, 256, 0, st>>>(a));
-    }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (n64)
+        HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_s2_bf16_kernel<NSX, 64, SCATTER, F16X>>(a.nblk, 256, 0, st, a)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16,
+                                       return hoig_launch<conv_halo_s2_bf16_kernel<NSX, 128, SCATTER, F16X>>(a.nblk, 256, 0, st, a)));
 }
 
 template <int KS>
@@ -1406,22 +1386,12 @@ int launch_halo(HaloArgs a, int ns, hipStream_t st) {
     const bool wide = a.nblk < 384;
     if (KS == 1) n64 ? HOIG_ROUTE_FD(a.f16, halo1_64) : (wide ? HOIG_ROUTE_FD(a.f16, halo1_128w) : HOIG_ROUTE_FD(a.f16, halo1_128));
     else n64 ? HOIG_ROUTE_FD(a.f16, same5_64) : (wide ? HOIG_ROUTE_FD(a.f16, same5_128w) : HOIG_ROUTE_FD(a.f16, same5_128));
-    if (n64) {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 64, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 64, false><<<a.nblk, 256, 0, st>>>(a));
-        HOIG_LAUNCH_CHECK();
-        return HOIG_OK;
-    }
+    if (n64)
+        HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_bf16_kernel<KS, NSX, 2, 64, F16X>>(a.nblk, 256, 0, st, a)));
     // fewer than ~1.5 workgroups per CU (wide): 8 waves per workgroup keep two waves on every SIMD
-    if (wide) {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 4, 128, true><<<a.nblk, 512, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 4, 128, false><<<a.nblk, 512, 0, st>>>(a));
-    } else {
-        if (a.f16) HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 128, true><<<a.nblk, 256, 0, st>>>(a));
-        else HOIG_NS_SWITCH(ns, conv_halo_bf16_kernel<KS, NSX, 2, 128, false><<<a.nblk, 256, 0, st>>>(a));
-    }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (wide)
+        HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_bf16_kernel<KS, NSX, 4, 128, F16X>>(a.nblk, 512, 0, st, a)));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return hoig_launch<conv_halo_bf16_kernel<KS, NSX, 2, 128, F16X>>(a.nblk, 256, 0, st, a)));
 }
 
 // a2 / cg1: the gathered tensor is [a | a2] along channels; c2 / n1: the output is [c | c2] (3x3 stride-1 halo kernel only:

@@ -348,32 +348,19 @@ constexpr int s2p_lds(int nsx) {
 template <int NSX, int BN, bool SCATTER, bool F16, int WM>
 int launch_s2p_one(const HaloArgs &a, hipStream_t st) {
     constexpr int shm = s2p_lds<BN, WM>(NSX);
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_halo_s2_m16p_kernel<NSX, BN, SCATTER, F16, WM>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, shm) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     if (WM == 4) SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p8_128) : HOIG_ROUTE_FD(F16, s2g_m16p8_128);
     else if (BN == 64) SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p4_64) : HOIG_ROUTE_FD(F16, s2g_m16p4_64);
     else SCATTER ? HOIG_ROUTE_FD(F16, s2s_m16p4_128) : HOIG_ROUTE_FD(F16, s2g_m16p4_128);
-    conv_halo_s2_m16p_kernel<NSX, BN, SCATTER, F16, WM><<<a.nblk, 128 * WM, shm, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<conv_halo_s2_m16p_kernel<NSX, BN, SCATTER, F16, WM>, shm>(a.nblk, 128 * WM, shm, st, a);
 }
 
 template <bool SCATTER, int WM>
 int launch_s2p(const HaloArgs &a, int ns, hipStream_t st) {
     if ((a.N % 128) != 0) {
-        if constexpr (WM == 2) {
-            if (a.f16) HOIG_NS_SWITCH(ns, return launch_s2p_one<NSX, 64, SCATTER, true, 2>(a, st));
-            HOIG_NS_SWITCH(ns, return launch_s2p_one<NSX, 64, SCATTER, false, 2>(a, st));
-        }
+        if constexpr (WM == 2) HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_s2p_one<NSX, 64, SCATTER, F16X, 2>(a, st)));
         return HOIG_EUNSUPPORTED;
     }
-    if (a.f16) HOIG_NS_SWITCH(ns, return launch_s2p_one<NSX, 128, SCATTER, true, WM>(a, st));
-    HOIG_NS_SWITCH(ns, return launch_s2p_one<NSX, 128, SCATTER, false, WM>(a, st));
+    HOIG_NS_SWITCH(ns, HOIG_F16_SWITCH(a.f16, return launch_s2p_one<NSX, 128, SCATTER, F16X, WM>(a, st)));
     return HOIG_EINVAL;
 }
 

@@ -673,45 +673,17 @@ int launch_gemm(const ThinArgs &a, int precision, hipStream_t st) {
     if (smem > 160 * 1024) return HOIG_EUNSUPPORTED;
     dim3 grid((unsigned)hoig_cdiv(a.ntiles, a.strip), a.CD / 64);
     HOIG_ROUTE_FD(FP16, thin);                      // (FP16: the forward's operand format; the data gradient runs on bf16)
-#define HOIG_THIN_GEMM(NT_, NW_)                                                                                         \
-    do {                                                                                                                 \
-        static hoig_once attr;                                                                                        \
-        if (!attr.done()) {                                                                                                     \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&thin_gemm_kernel<FP16, NT_, NW_>),                   \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)               \
-                return HOIG_ELAUNCH;                                                                                     \
-            attr.set();                                                                                                 \
-        }                                                                                                                \
-        thin_gemm_kernel<FP16, NT_, NW_><<<grid, NTHR, smem, st>>>(a);                                                   \
-    } while (0)
-    if (nt == 2 && nw == 2) HOIG_THIN_GEMM(2, 2);
-    else if (nt == 2) HOIG_THIN_GEMM(2, 1);
-    else HOIG_THIN_GEMM(1, 1);
-#undef HOIG_THIN_GEMM
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (nt == 2 && nw == 2) return hoig_launch<thin_gemm_kernel<FP16, 2, 2>, 160 * 1024>(grid, NTHR, smem, st, a);
+    if (nt == 2) return hoig_launch<thin_gemm_kernel<FP16, 2, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
+    return hoig_launch<thin_gemm_kernel<FP16, 1, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
 }
 
 template <int NPW, int WN>
 int launch_wgrad_t(const ThinArgs &a, int nt, int nd, dim3 grid, size_t smem, hipStream_t st) {
-#define HOIG_THIN_WG(NT_, ND_)                                                                                           \
-    do {                                                                                                                 \
-        static hoig_once attr;                                                                                        \
-        if (!attr.done()) {                                                                                                     \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&thin_wgrad_kernel<NPW, WN, NT_, ND_>),               \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)               \
-                return HOIG_ELAUNCH;                                                                                     \
-            attr.set();                                                                                                 \
-        }                                                                                                                \
-        thin_wgrad_kernel<NPW, WN, NT_, ND_><<<grid, NTHR, smem, st>>>(a);                                               \
-    } while (0)
-    if (nt == 2 && nd == 2) HOIG_THIN_WG(2, 2);
-    else if (nt == 2) HOIG_THIN_WG(2, 1);
-    else if (nd == 2) HOIG_THIN_WG(1, 2);
-    else HOIG_THIN_WG(1, 1);
-#undef HOIG_THIN_WG
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (nt == 2 && nd == 2) return hoig_launch<thin_wgrad_kernel<NPW, WN, 2, 2>, 160 * 1024>(grid, NTHR, smem, st, a);
+    if (nt == 2) return hoig_launch<thin_wgrad_kernel<NPW, WN, 2, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
+    if (nd == 2) return hoig_launch<thin_wgrad_kernel<NPW, WN, 1, 2>, 160 * 1024>(grid, NTHR, smem, st, a);
+    return hoig_launch<thin_wgrad_kernel<NPW, WN, 1, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
 }
 
 }  // namespace
@@ -824,27 +796,12 @@ int hoig_conv_thin_out(const hoig_conv_desc *d, const float *x, const float *w, 
     if (smem > 160 * 1024) return HOIG_EUNSUPPORTED;
     const unsigned grid = (unsigned)hoig_cdiv(a.ntiles, a.strip);
     HOIG_ROUTE_FD(!dgrad, thin_out);
-#define HOIG_THIN_OUT(FP16_, ND_, NW_)                                                                                   \
-    do {                                                                                                                 \
-        static hoig_once attr;                                                                                        \
-        if (!attr.done()) {                                                                                                     \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&thin_out_kernel<FP16_, ND_, NW_>),                   \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)               \
-                return HOIG_ELAUNCH;                                                                                     \
-            attr.set();                                                                                                 \
-        }                                                                                                                \
-        thin_out_kernel<FP16_, ND_, NW_><<<grid, NTHR, smem, st>>>(a);                                                   \
-    } while (0)
     if (!dgrad) {
-        if (nd == 2 && nw == 2) HOIG_THIN_OUT(true, 2, 2);
-        else if (nd == 2) HOIG_THIN_OUT(true, 2, 1);
-        else HOIG_THIN_OUT(true, 1, 1);
-    } else {
-        if (nd == 2 && nw == 2) HOIG_THIN_OUT(false, 2, 2);
-        else if (nd == 2) HOIG_THIN_OUT(false, 2, 1);
-        else HOIG_THIN_OUT(false, 1, 1);
+        if (nd == 2 && nw == 2) return hoig_launch<thin_out_kernel<true, 2, 2>, 160 * 1024>(grid, NTHR, smem, st, a);
+        if (nd == 2) return hoig_launch<thin_out_kernel<true, 2, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
+        return hoig_launch<thin_out_kernel<true, 1, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
     }
-#undef HOIG_THIN_OUT
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (nd == 2 && nw == 2) return hoig_launch<thin_out_kernel<false, 2, 2>, 160 * 1024>(grid, NTHR, smem, st, a);
+    if (nd == 2) return hoig_launch<thin_out_kernel<false, 2, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
+    return hoig_launch<thin_out_kernel<false, 1, 1>, 160 * 1024>(grid, NTHR, smem, st, a);
 }

@@ -396,25 +396,13 @@ extern "C" int hoig_conv2d_fwd_wino(const hoig_conv_desc *d, const float *x, con
     a.nblk_n = a.Co / W_CT;
     a.nblk = a.Bn * a.tiles_x * a.tiles_y * a.nblk_n;
     static const int ko_env = getenv("HOIG_WINO_KO") ? atoi(getenv("HOIG_WINO_KO")) : 0;
-    static hoig_once once;
-    if (!once.done()) {
-        bool ok = true;
-#define HOIG_WINO_ATTR(K_) ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino_kernel<K_>), \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS) == hipSuccess;
-        HOIG_WINO_ATTR(0) HOIG_WINO_ATTR(1) HOIG_WINO_ATTR(2) HOIG_WINO_ATTR(3) HOIG_WINO_ATTR(4) HOIG_WINO_ATTR(7)
-#undef HOIG_WINO_ATTR
-        if (!ok) return HOIG_ELAUNCH;
-        once.set();
-    }
     hipStream_t st = (hipStream_t)stream;
     switch (ko_env) {
-        case 1: conv_wino_kernel<1><<<a.nblk, W_NT, W_LDS, st>>>(a); break;
-        case 2: conv_wino_kernel<2><<<a.nblk, W_NT, W_LDS, st>>>(a); break;
-        case 3: conv_wino_kernel<3><<<a.nblk, W_NT, W_LDS, st>>>(a); break;
-        case 4: conv_wino_kernel<4><<<a.nblk, W_NT, W_LDS, st>>>(a); break;
-        case 7: conv_wino_kernel<7><<<a.nblk, W_NT, W_LDS, st>>>(a); break;
-        default: conv_wino_kernel<0><<<a.nblk, W_NT, W_LDS, st>>>(a);
+        case 1: return hoig_launch<conv_wino_kernel<1>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
+        case 2: return hoig_launch<conv_wino_kernel<2>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
+        case 3: return hoig_launch<conv_wino_kernel<3>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
+        case 4: return hoig_launch<conv_wino_kernel<4>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
+        case 7: return hoig_launch<conv_wino_kernel<7>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
+        default: return hoig_launch<conv_wino_kernel<0>, W_LDS>(a.nblk, W_NT, W_LDS, st, a);
     }
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
 }

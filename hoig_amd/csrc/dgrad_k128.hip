@@ -113,18 +113,9 @@ int launch_dgrad_thin(const float *dy, const unsigned short *wh, const unsigned 
     a.steps_per_wg = (int)hoig_cdiv(a.nsteps, split);
     split = (int)hoig_cdiv(a.nsteps, a.steps_per_wg);
     const size_t shm = (size_t)2 * ns_b(ns) * 8 * 2048;
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&dgrad_thin_k128_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&dgrad_thin_k128_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 32768) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&dgrad_thin_k128_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 32768) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     HOIG_ROUTE_D(k128);
-    HOIG_NS_SWITCH(ns, dgrad_thin_k128_kernel<NSX><<<dim3(mtiles, split), 256, shm, st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_NS_SWITCH(ns, return hoig_launch<dgrad_thin_k128_kernel<NSX>, (NSX == 2 ? 65536 : 32768)>(dim3(mtiles, split), 256, shm, st, a));
+    return HOIG_EINVAL;
 }
 
 }  // namespace hoig_detail

@@ -121,17 +121,12 @@ extern "C" int hoig_png_encode_u8(const uint8_t *src, int B, int H, int W, int C
     hipStream_t st = (hipStream_t)stream;
     uint8_t *ws = static_cast<uint8_t *>(workspace);
     const size_t lds = sizeof(PngSegShared) + (size_t)L.cap * sizeof(uint16_t);
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&png_segment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(sizeof(PngSegShared) + 32768 * sizeof(uint16_t))) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     png_filter_kernel<<<dim3((unsigned)hoig_cdiv(H, FILTER_ROWS), B), 64 * FILTER_ROWS, 0, st>>>(src, ws, L.per_image, H, W, C);
     HOIG_LAUNCH_CHECK();
-    png_segment_kernel<<<dim3((unsigned)L.nseg, B), PNG_LANES, lds, st>>>(ws, L, C, (int)png_row_stride(W, C));
-    HOIG_LAUNCH_CHECK();
+    constexpr int LDS_MAX = (int)(sizeof(PngSegShared) + 32768 * sizeof(uint16_t));
+    const int rc_seg = hoig_launch<png_segment_kernel, LDS_MAX>(dim3((unsigned)L.nseg, B), PNG_LANES, lds, st,
+                                                                ws, L, C, (int)png_row_stride(W, C));
+    if (rc_seg != HOIG_OK) return rc_seg;
     png_assemble_kernel<<<dim3((unsigned)L.nseg, B), PNG_LANES, 0, st>>>(ws, L, png_make_head(H, W, C), out, out_stride, sizes);
     HOIG_LAUNCH_CHECK();
     return HOIG_OK;

@@ -294,21 +294,10 @@ int launch_wgrad_dma(const WHaloArgs &a, int ns, dim3 grid, hipStream_t st) {
     if (a.tout || a.DB || ns == 2 || a.W % 32 || a.H % 4 || a.Ci % 32 || a.Co % 128 || a.pad != 1 || a.Hin != a.H || a.Win != a.W)
         return HOIG_EUNSUPPORTED;
     if (a.b_split > 0 && (a.X2 || a.b_split >= a.Bn || (a.b_split * a.tiles_x * a.tiles_y) % a.mt_per_split)) return HOIG_EUNSUPPORTED;
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_dma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                wgrad_dma_lds(2)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_dma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                wgrad_dma_lds(1)) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     if (a.b_split > 0) HOIG_ROUTE_W(wgrad_dma_pair);
     else HOIG_ROUTE_W(wgrad_dma);
-    if (ns == 3) wgrad_dma_kernel<2><<<grid, D_NT, wgrad_dma_lds(2), st>>>(a);
-    else wgrad_dma_kernel<1><<<grid, D_NT, wgrad_dma_lds(1), st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (ns == 3) return hoig_launch<wgrad_dma_kernel<2>, wgrad_dma_lds(2)>(grid, D_NT, wgrad_dma_lds(2), st, a);
+    return hoig_launch<wgrad_dma_kernel<1>, wgrad_dma_lds(1)>(grid, D_NT, wgrad_dma_lds(1), st, a);
 }
 
 }  // namespace hoig_detail

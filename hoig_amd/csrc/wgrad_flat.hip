@@ -359,20 +359,11 @@ int launch_wgrad_tile5(WFlatArgs a, int Bn, int ns, hipStream_t st) {
     if (splits > a.n_mtiles) splits = a.n_mtiles;
     a.mt_per_split = (int)hoig_cdiv(a.n_mtiles, splits);
     splits = (int)hoig_cdiv(a.n_mtiles, a.mt_per_split);
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_tile5_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, tile5_lds(1)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_tile5_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, tile5_lds(2)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_tile5_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, tile5_lds(3)) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     static_assert(tile5_lds(2) <= 160 * 1024, "both double-buffered images must fit in LDS");
     dim3 grid(a.nblk, splits);
     HOIG_ROUTE_W(wgrad_tile5);
-    HOIG_NS_SWITCH(ns, wgrad_tile5_kernel<NSX><<<grid, NT, tile5_lds(NSX), st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_tile5_kernel<NSX>, tile5_lds(NSX)>(grid, NT, tile5_lds(NSX), st, a));
+    return HOIG_EINVAL;
 }
 
 }  // namespace
@@ -396,19 +387,10 @@ int launch_wgrad_flat5(const float *x, const float *dy, float *dw, float *dbias,
     a.mt_per_split = (int)hoig_cdiv(a.n_mtiles, splits);
     splits = (int)hoig_cdiv(a.n_mtiles, a.mt_per_split);
     const int shm = ns_a(ns) * PTW * PSTR + ns_b(ns) * ((a.HPOS * QSTR + 255) / 256 * 256);
-    static hoig_once once;
-    if (!once.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_flat_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_flat_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_flat_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            return HOIG_ELAUNCH;
-        once.set();
-    }
     dim3 grid(a.nblk, splits);
     HOIG_ROUTE_W(wgrad_flat5);
-    HOIG_NS_SWITCH(ns, wgrad_flat_kernel<NSX><<<grid, NT, shm, st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_flat_kernel<NSX>, 128 * 1024>(grid, NT, shm, st, a));
+    return HOIG_EINVAL;
 }
 
 }  // namespace hoig_detail

@@ -585,18 +585,10 @@ int launch_wgrad_halo(const hoig_conv_desc *d, const float *x, const float *dy, 
     else cm == 2 ? HOIG_ROUTE_W(wgrad_halo_cm2) : HOIG_ROUTE_W(wgrad_halo_cm1);
     if (th4) {
         constexpr int LDS4 = 2 * (4 * 32 * 320) + (((6 * 34 * 64) + 255) / 256) * 256;      // dy hi, lo | x hi
-        static hoig_once once;
-        if (!once.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_halo_bf16_kernel<1, 3, 2, false, 4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS4) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_halo_bf16_kernel<3, 3, 2, false, 4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS4) != hipSuccess)
-                return HOIG_ELAUNCH;
-            once.set();
-        }
-        if (ns == 3) wgrad_halo_bf16_kernel<3, 3, 2, false, 4><<<grid, 768, LDS4, st>>>(a);
-        else wgrad_halo_bf16_kernel<1, 3, 2, false, 4><<<grid, 768, LDS4, st>>>(a);
-    } else if (s2 && cm == 2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 2, true><<<grid, 768, 0, st>>>(a));
+        if (ns == 3) return hoig_launch<wgrad_halo_bf16_kernel<3, 3, 2, false, 4>, LDS4>(grid, 768, LDS4, st, a);
+        return hoig_launch<wgrad_halo_bf16_kernel<1, 3, 2, false, 4>, LDS4>(grid, 768, LDS4, st, a);
+    }
+    if (s2 && cm == 2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 2, true><<<grid, 768, 0, st>>>(a));
     else if (s2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 1, true><<<grid, 384, 0, st>>>(a));
     else if (d->R == 5) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 5, 1><<<grid, 640, 0, st>>>(a));
     else if (cm == 2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 2><<<grid, 768, 0, st>>>(a));

@@ -298,7 +298,13 @@ def test_stride2_statically_walked_kernel_is_bit_identical(B, Ci, Co, H, transpo
         ops.set_precision('f32')
 
 
-@pytest.mark.parametrize('case', ['resblock_32', 'resblock_64', 'decoder_cat'])
+# the launcher each case runs on (conv_route.h): 128-channel tiles for the network's layers; 'full_res_64' is the one shape with 64-channel
+# tiles -- Co = 64 and 512 four-row tiles, which launch_halo3 asks for before it gives a 64-channel layer the 8-row tiling
+_NORMIN_ROUTE = {'resblock_32': 'fwd_halo3_m16_128_normin', 'resblock_64': 'fwd_halo3_m16_128_normin',
+                 'decoder_cat': 'fwd_halo3_m16_128_normin', 'full_res_64': 'fwd_halo3_m16_64_normin'}
+
+
+@pytest.mark.parametrize('case', ['resblock_32', 'resblock_64', 'decoder_cat', 'full_res_64'])
 def test_inference_norm_applied_by_the_consumers_loader(case):
     """ops.conv2d_after_norm (hoig_conv2d_fwd_packed_normin): conv3x3(relu(IN(x) * gamma + beta)) with the norm folded into the halo
     loader, against the same chain with the norm as a pass of its own -- same arithmetic up to the association of the fold (one FMA
@@ -313,6 +319,8 @@ def test_inference_norm_applied_by_the_consumers_loader(case):
             B, H, W, C1, C, Co = 8, 64, 64, 128, 128, 128
         elif case == 'resblock_64':
             B, H, W, C1, C, Co = 4, 64, 64, 0, 256, 256
+        elif case == 'full_res_64':
+            B, H, W, C1, C, Co = 8, 64, 128, 0, 64, 64
         else:
             B, H, W, C1, C, Co = 16, 32, 32, 0, 128, 256
         x = torch.randn(B, H, W, C, device='cuda', generator=g) * 2.0 + 0.7           # (a mean and a spread for the norm to remove)
@@ -324,6 +332,7 @@ def test_inference_norm_applied_by_the_consumers_loader(case):
         with torch.no_grad():
             y = ops.conv2d_after_norm(x, gamma, beta, w, bias, first=first, norm_next=False)
             assert y is not None, 'the layer should be on the 8-row tilings of the 16x16x32 kernel'
+            assert L.last_route(L.ROUTE_FWD) == _NORMIN_ROUTE[case]
             xn = ops.instance_norm(x, gamma, beta, act=L.ACT_RELU)
             if first is not None:
                 want = ops.conv2d_cat2(first, xn, w)

@@ -41,7 +41,8 @@ F32_128x32 = 'dgrad_igemm_f32_128x32'
 # kind: 'conv' (ops.conv2d / ops.conv_transpose2d, accumulate through hoig_conv2d_bwd_weight), 'fwd' (forward only: the activation
 # epilogues), 'fork' (ops.conv2d_fork: the second reader's gradient enters the data gradient), 'cat' (dw through
 # hoig_conv2d_cat_bwd_weight), 'split' / 'split_w' (dw -- and dx -- from pre-split dy), 'split_pair' / 'split_pair_w' (the grouped
-# forms), 'noscratch' (the thin weight gradient on a stream without a registered scratch block).
+# forms), 'noscratch' (the thin weight gradient on a stream without a registered scratch block), 'fwd_pair' (forward only: y of both
+# problems from hoig_conv2d_fwd_packed_pair, `fwd` being the route of that grouped launch).
 # wgrad / dgrad / fwd: the route asserted (a dict where it depends on the mode; None: not asserted for this row).
 ROWS = [
     # ---------------------------------------------------------------- weight gradient: launch_wgrad_halo by variant
@@ -49,7 +50,7 @@ ROWS = [
     row('halo_cm1_3tiles', C(3, 96, 192, 4, 96, 3, 1, 1, bias=Bs), 'wgrad_halo_cm1', 'dgrad_igemm_bf16_64x128'),
     row('halo_cm2_th2', C(2, 32, 128, 6, 64, 3, 1, 1, bias=Bs), 'wgrad_halo_cm2', F32_128x32),
     row('halo_th4', C(2, 512, 512, 32, 64, 3, 1, 1, bias=Bs), {'bf16x3': 'wgrad_halo_cm2', MIXED: 'wgrad_halo_th4'}),
-    row('halo_s2_cm1', C(2, 32, 64, 8, 64, 3, 2, 1, bias=Bs), 'wgrad_halo_s2_cm1', F32_128x32),
+    row('halo_s2_cm1', C(2, 32, 64, 8, 64, 3, 2, 1, bias=Bs), 'wgrad_halo_s2_cm1', F32_128x32, fwd='fwd_s2g_m16p4_64'),
     row('halo_s2_cm2', C(2, 32, 128, 12, 64, 3, 2, 1, bias=Bs), 'wgrad_halo_s2_cm2', F32_128x32),
     row('halo_tout', C(2, 128, 64, 6, 64, 3, 2, 1, T), 'wgrad_halo_tout', 'dgrad_igemm_bf16_64x128'),
     row('halo_tout_small', C(2, 128, 32, 4, 32, 3, 2, 1, T), 'wgrad_halo_tout', 'dgrad_s2g_m16p4_128'),
@@ -67,9 +68,11 @@ ROWS = [
     row('bf16_convT_off_halo', C(2, 128, 64, 5, 7, 3, 2, 1, T), 'wgrad_bf16_64', 'dgrad_igemm_bf16_64x128'),
     # ---------------------------------------------------------------- the fp32 weight gradient, also as the fallback of a 16-bit run
     row('f32_attn_128_25', C(2, 128, 25, 8, 8, 1, 1, 0, bias=Bs), 'wgrad_f32_32x128', modes=ALL3),
-    row('f32_d_first_19', C(2, 19, 64, 16, 16, 4, 2, 1, bias=Bs), 'wgrad_f32_64x128', F32_128x32, modes=ALL3),
+    row('f32_d_first_19', C(2, 19, 64, 16, 16, 4, 2, 1, bias=Bs), 'wgrad_f32_64x128', F32_128x32, fwd={'f32': 'fwd_igemm_f32_64x64'},
+        modes=ALL3),
     row('f32_32x64', C(2, 4, 16, 6, 6, 3, 1, 1, bias=Bs), 'wgrad_f32_32x64', F32_128x32, modes=ALL3),
-    row('f32_128x64', C(2, 3, 128, 10, 10, 3, 1, 1, bias=Bs), 'wgrad_f32_128x64', F32_128x32, modes=ALL3),
+    row('f32_128x64', C(2, 3, 128, 10, 10, 3, 1, 1, bias=Bs), 'wgrad_f32_128x64', F32_128x32, fwd={'f32': 'fwd_igemm_f32_64x128'},
+        modes=ALL3),
     row('f32_128x128', C(2, 16, 96, 6, 6, 3, 1, 1, bias=Bs), 'wgrad_f32_128x128', F32_128x32, modes=('f32',)),
     row('f32_32x128', C(2, 16, 24, 6, 6, 3, 1, 1, bias=Bs), 'wgrad_f32_32x128', F32_128x32, fwd='fwd_igemm_f32_128x32', modes=('f32',)),
     row('f32_64x128', C(2, 16, 48, 6, 6, 3, 1, 1, bias=Bs), 'wgrad_f32_64x128', F32_128x32, modes=('f32',)),
@@ -203,6 +206,15 @@ ROWS += [
     row('act_halo5_relu', C(2, 32, 128, 8, 72, 5, 1, 0, bias=Bs, act='relu'), fwd='fwd_halo5_m16', kind='fwd'),      # (an activation: no K split)
     row('act_s2g_relu', C(2, 32, 128, 8, 64, 3, 2, 1, bias=Bs, act='relu'), fwd='fwd_s2g_m16p4_128', kind='fwd'),
     row('act_s2g_p8_lrelu', C(4, 32, 128, 128, 512, 3, 2, 1, bias=Bs, act='lrelu'), fwd='fwd_s2g_m16p8_128', kind='fwd'),
+    row('act_thin_out_tanh', C(2, 64, 3, 8, 64, 3, 1, 1, bias=Bs, act='tanh'), fwd='fwd_thin_out', kind='fwd'),
+    # ConvTranspose2d onto 64-channel tiles: on three terms it stays on the 32x32 kernel (fwd_s2s_64 above, launch_halo_s2), so the
+    # 16x16x32 forms are reached by a TWO-term forward only -- at most one workgroup per CU the 4-row form, above that (and N % 128 != 0,
+    # which rules out the 8-row form) the kernel of conv_halo16.hip
+    row('fwd_s2s_p4_64_f16x2', C(2, 32, 64, 4, 32, 3, 2, 1, T), fwd='fwd_s2s_m16p4_64', kind='fwd', modes=('f16x2',)),
+    row('fwd_s2s_m16_64_f16x2', C(5, 32, 64, 32, 64, 3, 2, 1, T), fwd='fwd_s2s_m16_64', kind='fwd', modes=('f16x2',)),
+    # the grouped forward on 64-channel tiles, through its entry point: ops.conv2d_pair never gets here (pair_ok asks for Co % 128 == 0);
+    # Co = 64 needs 2 B (W / 32) (H / 4) >= 512 workgroups for the 8-row tiling
+    row('fwd_pair_64', C(2, 32, 64, 64, 256, 3, 1, 1, bias=Bs), fwd='fwd_halo3_m16_64_pair', kind='fwd_pair', modes=(MIXED,)),
 ]
 
 # ---- the thin-channel layers (conv_thin.hip): one row per fragment-count class of hoig_conv_thin_wgrad (nfr = ceil(R*S*F / 32): 1, 2,
@@ -222,6 +234,18 @@ ROWS.append(row('thin_out_no_scratch', C(2, 64, 3, 8, 96, 7, 1, 3), 'wgrad_thin_
 # Routes that no row of this file reaches, with the reason and the test that pins them.  The completeness test below caps it: no
 # weight-gradient route, at most one data-gradient route in five.
 NOT_PINNED_HERE = {}
+
+# Forward routes that no row of this file reaches and another test asserts: route -> 'tests/<file>::<test>'.
+ASSERTED_ELSEWHERE = {
+    'fwd_f6_64': 'tests/test_conv_f6_gpu.py::test_every_f6_route_has_a_row',
+    'fwd_f6_128': 'tests/test_conv_f6_gpu.py::test_every_f6_route_has_a_row',
+    'fwd_f6_64_normin': 'tests/test_conv_f6_gpu.py::test_every_f6_route_has_a_row',
+    'fwd_f6_128_normin': 'tests/test_conv_f6_gpu.py::test_every_f6_route_has_a_row',
+    'fwd_igemm_m16_64x128': 'tests/test_conv_f6_gpu.py::test_refused_shapes_touch_nothing_and_run_on_three_terms',
+    'fwd_halo3_m16_128_pair': 'tests/test_conv_composites_gpu.py::test_conv2d_pair',
+    'fwd_halo3_m16_64_normin': 'tests/test_conv_m16_gpu.py::test_inference_norm_applied_by_the_consumers_loader',
+    'fwd_halo3_m16_128_normin': 'tests/test_conv_m16_gpu.py::test_inference_norm_applied_by_the_consumers_loader',
+}
 
 
 def _p(t):
@@ -336,6 +360,23 @@ def check_row(r, mode, report=None):
         err['y'] = gpu_util.rel_err(y, ref['y'])
         assert err['y'] < bounds['y'][0], ('y', err['y'], bounds['y'])
         if r.kind == 'fwd':
+            return report
+        if r.kind == 'fwd_pair':
+            # the second problem of the grouped launch: its own operands (another seed)
+            ref2 = _reference(c._replace(seed=c.seed + 1))
+            xb, wb, bb = ref2['x'].cuda(), ops.pack_weight(ref2['w'].cuda(), False), ref2['b'].cuda() if c.bias else None
+            (ha, la), (hb, lb) = ops._packed_planes(wd.detach(), False, False), ops._packed_planes(wb, False, False)
+            ya, yb = torch.empty_like(y), torch.empty_like(y)
+            d = _desc(L, c, ops.precision)
+            L.call('hoig_conv2d_fwd_packed_pair', ctypes.byref(d), _p(xd.detach()), _p(xb), _p(ha), _p(la), _p(hb), _p(lb),
+                   _p(bd.detach()) if c.bias else None, _p(bb), _p(ya), _p(yb), st)
+            torch.cuda.synchronize()
+            report['routes_entry'] = {'y': L.last_route(L.ROUTE_FWD)}
+            want = _want(r.fwd, mode)
+            assert report['routes_entry']['y'] == want, '%s: y ran on %r, the row was shaped for %r' % (r.id, report['routes_entry']['y'], want)
+            for key, got, truth in (('y_entry', ya, ref['y']), ('y_b_entry', yb, ref2['y'])):
+                err[key] = gpu_util.rel_err(got, truth)
+                assert err[key] < bounds['y'][0], (key, err[key], bounds['y'])
             return report
         dx_ref = ref['dx'] if gx is None else ref['dx'] + gx.cpu().double()
         err['dx'] = gpu_util.rel_err(xd.grad, dx_ref)
@@ -464,3 +505,29 @@ def test_every_backward_route_has_a_row():
     assert not missing, 'routes without a row and without a reason: %r' % sorted(missing)
     assert not set(NOT_PINNED_HERE) & wgrad, 'every weight-gradient route is pinned here'
     assert 5 * len(set(NOT_PINNED_HERE) & dgrad) <= len(dgrad)
+
+
+def test_every_forward_route_has_a_row():
+    """Every forward id of the library's route table is claimed by a row above, or asserted by the test ASSERTED_ELSEWHERE names (whose
+    file must hold the route's name), or listed in NOT_PINNED_HERE with the dispatcher condition that shadows it: at most 3 of them."""
+    import os
+    import re
+    from hoig_amd import _lib as L
+    fwd = {n for n in L.route_names() if n.startswith('fwd_')}
+    assert len(fwd) >= 58, 'the route table lost its ids'
+    claimed = _claimed(r.fwd for r in ROWS)
+    assert claimed <= fwd, 'a row names a route the library does not have: %r' % sorted(claimed - fwd)
+    assert set(ASSERTED_ELSEWHERE) <= fwd
+    assert not set(ASSERTED_ELSEWHERE) & claimed, 'listed as asserted elsewhere, yet a row claims it'
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for route, where in ASSERTED_ELSEWHERE.items():
+        path, name = where.split('::')
+        with open(os.path.join(root, path)) as f:
+            text = f.read()
+        assert re.search(r'^def %s\(' % re.escape(name), text, re.M), '%s has no %s' % (path, name)
+        assert "'%s'" % route in text, '%s does not name %s' % (path, route)
+    shadowed = set(NOT_PINNED_HERE) & fwd
+    assert not shadowed & (claimed | set(ASSERTED_ELSEWHERE)), 'listed as not pinned, yet asserted'
+    missing = fwd - claimed - set(ASSERTED_ELSEWHERE) - shadowed
+    assert not missing, 'forward routes without a row and without a reason: %r' % sorted(missing)
+    assert len(shadowed) <= 3
