@@ -21,6 +21,7 @@ POOL_MAX, POOL_AVG = 0, 1
 JPEG_SUBSEQ_BYTES = 64              # HOIG_JPEG_SUBSEQ_BYTES
 PNG_SEGMENT_BYTES = 8192            # HOIG_PNG_SEGMENT_BYTES
 GEMM_ACCUMULATE, GEMM_SYMMETRIC, GEMM_F32 = 1, 2, 4      # HOIG_GEMM_*
+FM_NONFINITE, FM_CLAMPED = 1, 2     # the bits of a feature-metric status word (feature_metrics.h)
 # HOIG_PNG_E*: the bits of a PNG decoder status word
 PNG_ECODE, PNG_EBTYPE, PNG_ESTORED, PNG_EDIST, PNG_EEARLY, PNG_EMORE, PNG_ELESS, PNG_EFILTER, PNG_EADLER = 1, 2, 4, 8, 16, 32, 64, 128, 256
 _ERR = {EINVAL: 'invalid argument', ELAUNCH: 'kernel launch failed', EUNSUPPORTED: 'unsupported shape'}
@@ -184,6 +185,14 @@ _SIGS = {
     'hoig_tridiag_eigvals_f64': [_vp, _vp, _i, _vp, _vp],
     'hoig_tridiag_eigvals_f64_host': [_vp, _vp, _i, _vp],
     'hoig_sym_tridiag_f64_host': [_vp, _i64, _i, _vp, _vp],
+    'hoig_kid_poly_f64': [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _i64, _vp],
+    'hoig_kid_poly_f64_host': [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp],
+    'hoig_kid_finish_f64': [_vp, _i, _i, _vp, _vp, _vp],
+    'hoig_kid_finish_f64_host': [_vp, _i, _i, _vp, _vp],
+    'hoig_knn_radius_f64': [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp],
+    'hoig_knn_radius_f64_host': [_vp, _i, _i, _vp, _i, _vp, _vp],
+    'hoig_manifold_hits_f64': [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp],
+    'hoig_manifold_hits_f64_host': [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp],
     'hoig_grad_stats_chunk': [],
     'hoig_grad_stats_max_grid': [],
     'hoig_grad_stats': [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp],
@@ -256,6 +265,12 @@ def _load():
     lib.hoig_pchol_f64_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_sym_eigvals_f64_workspace_bytes.argtypes = [_i]
     lib.hoig_sym_eigvals_f64_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_kid_workspace_bytes.argtypes = [_i, _i]
+    lib.hoig_kid_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_knn_workspace_bytes.argtypes = [_i]
+    lib.hoig_knn_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_manifold_hits_workspace_bytes.argtypes = [_i, _i]
+    lib.hoig_manifold_hits_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_grad_stats_workspace_bytes.argtypes = [_i64, _i]
     lib.hoig_grad_stats_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]

@@ -14,6 +14,7 @@ import torch
 
 from . import kernels as K
 from .fid import calculate_frechet_distance, compute_statistics_of_path
+from .feature_metrics import FeatureBank, _options, kid_from_features, precision_recall_from_features
 from .fid_device import Moments, fid_device_option, frechet_distance_device
 from .ssim import ssim_pairs_u8
 
@@ -48,10 +49,16 @@ class Scorer(object):
 
     fid_device (HOIG_DEVICE_FID=1; off by default): the features go into streaming fp64 moments on the device (fid_device.Moments:
     update() makes no host copy and does not wait for the device) and result() takes the distance with
-    fid_device.frechet_distance_device.  The values are then close to the directory functions', not equal (docs/fid_device.md)."""
+    fid_device.frechet_distance_device.  The values are then close to the directory functions', not equal (docs/fid_device.md).
+
+    kid, prc (off by default; True, or a dict of the keyword arguments of feature_metrics.kid_from_features /
+    precision_recall_from_features): the features of both streams are also kept on the device (feature_metrics.FeatureBank, 4 * dims
+    bytes per image and stream) and result() gains 'kid', 'kid_std' and 'precision', 'recall', 'density', equal to
+    calculate_kid_given_paths / calculate_prc_given_paths on the directories (docs/feature_metrics.md).  Both need the FID network and
+    the ground truth's features, so neither goes with fid_reference."""
 
     def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None,
-                 fid_device=None):
+                 fid_device=None, kid=None, prc=None):
         self.fid, self.lpips, self.ssim, self.img_size = fid, lpips, bool(ssim), img_size
         self.n = 0
         if isinstance(fid_reference, str):
@@ -60,6 +67,14 @@ class Scorer(object):
             fid_reference = compute_statistics_of_path(fid_reference, None, None, None)
         self.fid_reference = fid_reference
         self.fid_device = False
+        self.kid, self.prc = _options(kid, 'kid'), _options(prc, 'prc')
+        self._bank_gen = self._bank_gt = None
+        if self.kid is not None or self.prc is not None:
+            if fid is None:
+                raise ValueError('kid / prc need the FID network: Scorer(fid=InceptionFeatures(...), ...)')
+            if fid_reference is not None:
+                raise ValueError('kid / prc need the ground truth\'s features, which a fid_reference replaces')
+            self._bank_gen, self._bank_gt = FeatureBank(fid.dims, fid.device), FeatureBank(fid.dims, fid.device)
         if fid is not None:
             self._fid_gen, self._fid_gt = _Batches(fid_batch), (_Batches(fid_batch) if fid_reference is None else None)
             self._feat_gen, self._feat_gt = [], []
@@ -76,8 +91,15 @@ class Scorer(object):
         self._lpips_means, self._ssim, self._ms_ssim = [], [], []
 
     # ---- one batch, as the path functions run it
-    def _features(self, u8):
-        return self.fid.features_u8(u8.contiguous()).double().cpu().numpy()
+    def _features_device(self, u8, bank=None):
+        """fp32 [B, dims] on the device; with kid / prc on, a copy goes into the stream's bank."""
+        f = self.fid.features_u8(u8.contiguous())
+        if bank is not None:
+            bank.append(f)
+        return f
+
+    def _features(self, u8, bank=None):
+        return self._features_device(u8, bank).double().cpu().numpy()
 
     def _pair(self, metrics, gen, gt, into):
         u8 = K.pil_resize_chain_u8(torch.cat([gen, gt]), self.img_size)
@@ -97,14 +119,14 @@ class Scorer(object):
         self.n += gen_u8.shape[0]
         if self.fid is not None and self.fid_device:
             for b in self._fid_gen.push(gen_u8):
-                self._feat_gen.update(self.fid.features_u8(b.contiguous()))
+                self._feat_gen.update(self._features_device(b, self._bank_gen))
             if self._fid_gt is not None:
                 for b in self._fid_gt.push(gt_u8):
-                    self._feat_gt.update(self.fid.features_u8(b.contiguous()))
+                    self._feat_gt.update(self._features_device(b, self._bank_gt))
         elif self.fid is not None:
-            self._feat_gen += [self._features(b) for b in self._fid_gen.push(gen_u8)]
+            self._feat_gen += [self._features(b, self._bank_gen) for b in self._fid_gen.push(gen_u8)]
             if self._fid_gt is not None:
-                self._feat_gt += [self._features(b) for b in self._fid_gt.push(gt_u8)]
+                self._feat_gt += [self._features(b, self._bank_gt) for b in self._fid_gt.push(gt_u8)]
         into = (self._lpips_means, self._ssim, self._ms_ssim)
         for size, metrics in self._pairs.items():
             bg, bt = self._pair_batches[size]
@@ -119,6 +141,12 @@ class Scorer(object):
         if moments.n == 0:
             raise ValueError('no images were given')
         return moments
+
+    def _rows(self, bank, batches):
+        """A stream's feature rows with the short last batch in: that batch goes into a COPY of the bank, as in _moments."""
+        if batches.rest is not None:
+            bank = bank.copy().append(self.fid.features_u8(batches.rest.contiguous()))
+        return bank.rows()
 
     def _statistics(self, feats, batches):
         if self.fid_device:
@@ -152,6 +180,12 @@ class Scorer(object):
         elif self.fid is not None:
             ref = self.fid_reference if self.fid_reference is not None else self._statistics(self._feat_gt, self._fid_gt)
             out['fid'] = calculate_frechet_distance(*(self.statistics() + tuple(ref)))
+        if self._bank_gen is not None:
+            gen, gt = self._rows(self._bank_gen, self._fid_gen), self._rows(self._bank_gt, self._fid_gt)
+            if self.kid is not None:
+                out['kid'], out['kid_std'] = kid_from_features(gen, gt, **self.kid)
+            if self.prc is not None:
+                out.update(precision_recall_from_features(gt, gen, **self.prc))
         into = (list(self._lpips_means), list(self._ssim), list(self._ms_ssim))
         for size, metrics in self._pairs.items():
             bg, bt = self._pair_batches[size]

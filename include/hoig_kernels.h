@@ -858,6 +858,54 @@ int hoig_tridiag_eigvals_f64(const double *d, const double *e, int n, double *la
 int hoig_tridiag_eigvals_f64_host(const double *d, const double *e, int n, double *lambda);
 int hoig_sym_tridiag_f64_host(const double *A, int64_t lda, int n, double *d, double *e);
 
+/* ---- FEATURE-SPACE METRICS IN FP64: KID AND PRECISION / RECALL (hoig_amd/csrc/feature_metrics.hip, feature_metrics.h,
+ *      feature_metrics_host.cpp; hoig_amd/metrics/feature_metrics.py; docs/feature_metrics.md).  Feature sets are row-major fp32
+ *      [n][D], any D >= 1; every product is a 64 x 64 tile of P Q^T on v_mfma_f64_16x16x4_f64 from rows staged through LDS, and no tile
+ *      is stored.  No floating-point atomics, no grid-wide wait: every sum has one owner and a fixed order.  A status word (one int32 in
+ *      device memory, written by the call) is 0 or an OR of 1: a non-finite feature was read, 2: an index of a gather table lay
+ *      outside its set and was clamped into it.  Every device entry never synchronises and allocates nothing; workspaces are 8-byte
+ *      aligned device memory of at least the stated size.  The *_host twins take host memory, make no HIP call and walk the same
+ *      tiles, lanes and reductions; their dot products are summed in order of k, so tile values are close to the device's, not
+ *      equal, while every reduction of tile values is the device's bit for bit. ---- */
+/* S * 3 * ceil(m / 64)^2 doubles: one partial per (subset, term, tile) -- O(tiles), never O(m^2).  HOIG_EINVAL for S < 1, S > 65535
+ * or m < 2. */
+int64_t hoig_kid_workspace_bytes(int S, int m);
+/* The polynomial-kernel sums of KID for S subsets at once.  k(a, b) = (gamma a.b + coef0)^degree, degree in 1 .. 4 by repeated
+ * multiplication.  Subset s is the rows ix[s][0 .. m) of X [nx][D] and iy[s][0 .. m) of Y [ny][D] (int32 tables in device memory; an
+ * index is clamped into its set before every read, which also sets status bit 2).  out[s] = {sum_{i != j} k(x_i, x_j),
+ * sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j), mmd^2} with mmd^2 = (Sxx / (m (m - 1)) + Syy / (m (m - 1))) - 2 Sxy / m^2; i and j
+ * are positions in the subset, and i == j is left out by position.  Grid (tile, term, subset): xx and yy run the tiles on and above
+ * the diagonal only and count the others twice; a workgroup leaves one partial at its own slot and hoig_kid_finish_f64, one wave per
+ * subset, adds the slots in slot order.  A non-zero status makes every entry of out NaN.  Two launches.
+ * HOIG_EINVAL, and nothing launched: a NULL pointer, a size below 1, m < 2, S > 65535, degree outside 1 .. 4, a small workspace. */
+int hoig_kid_poly_f64(const float *X, int nx, const float *Y, int ny, int D, const int32_t *ix, const int32_t *iy, int S, int m,
+                      double gamma, double coef0, int degree, double *out, int32_t *status, void *workspace, int64_t workspace_bytes,
+                      hoig_stream_t stream);
+int hoig_kid_poly_f64_host(const float *X, int nx, const float *Y, int ny, int D, const int32_t *ix, const int32_t *iy, int S, int m,
+                           double gamma, double coef0, int degree, double *out, int32_t *status);
+/* The finishing stage alone: partials [S][3][nt * nt] (nt = ceil(m / 64), slot ti * nt + tj; of xx and yy only the slots with
+ * tj >= ti are read) -> out [S][4].  Lane l of the subset's wave adds slots l, l + 64, .. in order, then the 64 lane sums meet in the
+ * butterfly of fid_stats.h: a function of the partials alone.  status may be NULL (taken as 0). */
+int hoig_kid_finish_f64(const double *partials, int S, int m, const int32_t *status, double *out, hoig_stream_t stream);
+int hoig_kid_finish_f64_host(const double *partials, int S, int m, const int32_t *status, double *out);
+/* radius[i] = the k-th smallest of d2(x_i, x_j) over j != i (left out by index, not by value), 1 <= k <= min(8, n - 1), for the rows
+ * of X [n][D].  d2 = max(0, (|x|^2 + |y|^2) - 2 x.y) in fp64 on operands (double)x - pivot[c] (pivot: D doubles, or NULL; distances
+ * do not depend on it, the cancellation does).  Grid (row tile, column chunk): a chunk leaves its 8 smallest candidates per row in the
+ * workspace and a merge kernel takes the k-th of them all; the k smallest of a multiset do not depend on the order.  A non-zero
+ * status makes every radius NaN.  Three launches.  HOIG_EINVAL: a NULL pointer, n < 2, D < 1, k out of range, a small workspace. */
+int64_t hoig_knn_workspace_bytes(int n);
+int hoig_knn_radius_f64(const float *X, int n, int D, const double *pivot, int k, double *radius, int32_t *status, void *workspace,
+                        int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_knn_radius_f64_host(const float *X, int n, int D, const double *pivot, int k, double *radius, int32_t *status);
+/* hits[j] = the number of rows i of X [nx][D] with d2(x_i, y_j) <= radius[i], for the rows of Y [ny][D]; d2 and pivot as above.
+ * Grid (probe tile, row chunk): per-chunk int32 counts in the workspace, added by a second kernel; integer sums do not depend on the
+ * order.  With a non-zero status the counts are unspecified.  Four launches. */
+int64_t hoig_manifold_hits_workspace_bytes(int nx, int ny);
+int hoig_manifold_hits_f64(const float *X, int nx, const double *radius, const float *Y, int ny, int D, const double *pivot,
+                           int32_t *hits, int32_t *status, void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_manifold_hits_f64_host(const float *X, int nx, const double *radius, const float *Y, int ny, int D, const double *pivot,
+                                int32_t *hits, int32_t *status);
+
 /* ---- GRADIENT GUARD: STATISTICS, SKIP-STEP AND NORM CLIPPING ON THE DEVICE (hoig_amd/csrc/grad_guard.hip, grad_guard.h,
  *      grad_guard_host.cpp; hoig_amd/guard.py; docs/grad_guard.md).  The *_host twins take host memory, make no HIP call and walk
  *      every sum in the device's order: their results are the device's, bit for bit. ---- */
