@@ -218,6 +218,21 @@ _SIGS = {
     'hoig_daug_fwd_host': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     'hoig_daug_bwd': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     'hoig_daug_bwd_host': [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    'hoig_swd_levels': [_i, _i],
+    'hoig_swd_positions': [ctypes.c_uint64, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp],
+    'hoig_swd_positions_host': [ctypes.c_uint64, _i, _i64, _i, _i, _i, _i, _i, _vp],
+    'hoig_swd_descriptors_u8': [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp],
+    'hoig_swd_descriptors_u8_host': [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    'hoig_swd_channel_stats_f64': [_vp, _i64, _vp, _vp, _vp, _i64, _vp],
+    'hoig_swd_channel_stats_f64_host': [_vp, _i64, _vp, _vp],
+    'hoig_swd_project_f32': [_vp, _i64, _vp, _vp, _i, _vp, _vp],
+    'hoig_swd_project_f32_host': [_vp, _i64, _vp, _vp, _i, _vp],
+    'hoig_sort_segments_f32': [_vp, _i64, _i64, _vp, _vp, _vp],
+    'hoig_sort_segments_f32_host': [_vp, _i64, _i64, _vp],
+    'hoig_sort_segments_lds_max': [],
+    'hoig_sort_segments_tile': [],
+    'hoig_swd_sorted_l1_f64': [_vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    'hoig_swd_sorted_l1_f64_host': [_vp, _vp, _i64, _vp],
 }
 
 
@@ -271,6 +286,14 @@ def _load():
     lib.hoig_knn_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_manifold_hits_workspace_bytes.argtypes = [_i, _i]
     lib.hoig_manifold_hits_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_swd_descriptors_workspace_bytes.argtypes = [_i] * 4
+    lib.hoig_swd_descriptors_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_swd_channel_stats_workspace_bytes.argtypes = [_i64]
+    lib.hoig_swd_channel_stats_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_sort_segments_workspace_bytes.argtypes = [_i64, _i64]
+    lib.hoig_sort_segments_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_swd_sorted_l1_workspace_bytes.argtypes = [_i64]
+    lib.hoig_swd_sorted_l1_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_grad_stats_workspace_bytes.argtypes = [_i64, _i]
     lib.hoig_grad_stats_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
@@ -290,6 +313,9 @@ lib = _load()
 
 DAUG_COLOR, DAUG_TRANSLATION, DAUG_CUTOUT = 1, 2, 4      # HOIG_DAUG_*: the bits of a record's flags and of the policy word
 DAUG_STATE_WORDS, DAUG_MAX_PARTS = 16, 16                # HOIG_DAUG_STATE_WORDS, HOIG_DAUG_MAX_PARTS
+SWD_K, SWD_DEGENERATE, SORT_NAN = 147, 7, 8             # HOIG_SWD_K; the status bits HOIG_SWD_DEGENERATE (1 << channel), HOIG_SORT_NAN
+SORT_LDS_MAX = lib.hoig_sort_segments_lds_max()          # HOIG_SORT_LDS_MAX: the longest segment of the sort's LDS route
+SORT_TILE = lib.hoig_sort_segments_tile()                # HOIG_SORT_TILE: keys of a tile of its multi-pass route
 GUARD_SKIP = 1                                   # HOIG_GUARD_SKIP
 GRAD_CHUNK = lib.hoig_grad_stats_chunk()         # HOIG_GRAD_CHUNK: elements of a stage-1 chunk of hoig_grad_stats
 GRAD_MAX_GRID = lib.hoig_grad_stats_max_grid()   # the most workgroups its stage 1 uses

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "hoig_kernels.h"
+#include "philox.h"
 
 #if defined(__HIPCC__)
 #define DAUG_HD __host__ __device__
@@ -42,17 +43,9 @@ DAUG_HD inline uint64_t daug_u64(double d) {
     return c.u;
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011, Random123)
+// ---- Philox4x32-10 (philox.h: the routine the sliced Wasserstein distance shares)
 DAUG_HD inline void daug_philox(const uint32_t ctr[4], uint32_t k0, uint32_t k1, uint32_t out[4]) {
-    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+    hoig_philox4x32_10(ctr, k0, k1, out);
 }
 
 DAUG_HD inline float daug_uniform(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }      // (w >> 8) * 2^-24, exact

@@ -1,6 +1,7 @@
 """python -m hoig_amd.metrics {fid,lpips,ssim} PATH1 PATH2: what metrics/pytorch_fid, metrics/lpips.py and metrics/ssim.py print;
 kid, prc: the Kernel Inception Distance and precision / recall / density of PATH1 (generated) against PATH2 (real) on the same
-Inception features (docs/feature_metrics.md)."""
+Inception features (docs/feature_metrics.md); swd: the Laplacian-pyramid sliced Wasserstein distance of PATH1 against PATH2, which
+needs no weights (docs/swd.md)."""
 import argparse
 import os
 import sys
@@ -10,9 +11,9 @@ DIMS = (64, 192, 768, 2048)
 
 def parser():
     p = argparse.ArgumentParser(prog='python -m hoig_amd.metrics', description=__doc__)
-    p.add_argument('metric', choices=('fid', 'lpips', 'ssim', 'kid', 'prc'))
+    p.add_argument('metric', choices=('fid', 'lpips', 'ssim', 'kid', 'prc', 'swd'))
     p.add_argument('path', nargs=2, help='two image directories (fid: or .npz statistics)')
-    p.add_argument('--batch-size', type=int, default=None, help='fid / lpips / kid / prc: 50, ssim: 1 (the reference defaults)')
+    p.add_argument('--batch-size', type=int, default=None, help='fid / lpips / kid / prc / swd: 50, ssim: 1 (the reference defaults)')
     p.add_argument('--dims', type=int, default=2048, choices=DIMS, help='fid / kid / prc: Inception feature dimensionality')
     p.add_argument('--img-size', type=int, default=256, help='lpips / ssim: first resize of get_eval_loader')
     p.add_argument('--device', default=None)
@@ -32,6 +33,11 @@ def parser():
     p.add_argument('--kid-subset-size', type=int, default=1000, help='kid: rows per subset (at most the smaller directory)')
     p.add_argument('--kid-seed', type=int, default=0, help='kid: seed of the subset draws')
     p.add_argument('--prc-k', type=int, default=3, help='prc: the nearest neighbour that sets a ball\'s radius (1 .. 8)')
+    p.add_argument('--swd-patches', type=int, default=128, help='swd: patches per image and level')
+    p.add_argument('--swd-repeats', type=int, default=4, help='swd: sets of directions')
+    p.add_argument('--swd-dirs', type=int, default=128, help='swd: directions per set')
+    p.add_argument('--swd-levels', type=int, default=None, help='swd: at most this many pyramid levels (default: down to 16 pixels)')
+    p.add_argument('--swd-seed', type=int, default=0, help='swd: seed of the patch positions and of the directions')
     return p
 
 
@@ -58,6 +64,11 @@ def main(argv=None):
         v = calculate_prc_given_paths(a.path, a.batch_size or 50, a.device, a.dims, a.inception_weights, a.precision,
                                       device_png_decode=a.device_png_decode, k=a.prc_k)
         print('Precision: ', v['precision'], ' Recall: ', v['recall'], ' Density: ', v['density'])
+    elif a.metric == 'swd':
+        from .swd import calculate_swd_given_paths
+        v = calculate_swd_given_paths(a.path, a.batch_size or 50, a.device, device_png_decode=a.device_png_decode,
+                                      patches=a.swd_patches, repeats=a.swd_repeats, dirs=a.swd_dirs, levels=a.swd_levels, seed=a.swd_seed)
+        print('SWD: ', v['swd'], '', ' '.join(repr(x) for x in v['swd_levels']))    # (the mean, then the levels, finest first)
     elif a.metric == 'lpips':
         from .lpips import calculate_lpips_given_paths
         v = calculate_lpips_given_paths(a.path, a.img_size, a.batch_size or 50, a.alexnet_weights, a.lpips_weights, a.precision,

@@ -17,6 +17,7 @@ from .fid import calculate_frechet_distance, compute_statistics_of_path
 from .feature_metrics import FeatureBank, _options, kid_from_features, precision_recall_from_features
 from .fid_device import Moments, fid_device_option, frechet_distance_device
 from .ssim import ssim_pairs_u8
+from .swd import banks_for, swd_from_banks, swd_options
 
 
 class _Batches(object):
@@ -55,10 +56,16 @@ class Scorer(object):
     precision_recall_from_features): the features of both streams are also kept on the device (feature_metrics.FeatureBank, 4 * dims
     bytes per image and stream) and result() gains 'kid', 'kid_std' and 'precision', 'recall', 'density', equal to
     calculate_kid_given_paths / calculate_prc_given_paths on the directories (docs/feature_metrics.md).  Both need the FID network and
-    the ground truth's features, so neither goes with fid_reference."""
+    the ground truth's features, so neither goes with fid_reference.
+
+    swd (off by default; True, or a dict of patches, repeats, dirs, levels, seed): the Laplacian-pyramid sliced Wasserstein distance
+    between the two streams (swd.py, docs/swd.md).  It needs no network -- Scorer(fid=None, lpips=None, ssim=False, swd=True) runs
+    without any weights.  update() keeps each image's patch descriptors on the device (swd.SWDBank, 4 * 147 * patches * levels bytes
+    per image and stream) and result() gains 'swd' and 'swd_levels', equal to calculate_swd_given_paths on the directories whatever
+    the sizes of the update() calls."""
 
     def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None,
-                 fid_device=None, kid=None, prc=None):
+                 fid_device=None, kid=None, prc=None, swd=None):
         self.fid, self.lpips, self.ssim, self.img_size = fid, lpips, bool(ssim), img_size
         self.n = 0
         if isinstance(fid_reference, str):
@@ -69,6 +76,8 @@ class Scorer(object):
         self.fid_device = False
         self.kid, self.prc = _options(kid, 'kid'), _options(prc, 'prc')
         self._bank_gen = self._bank_gt = None
+        self.swd = swd_options(swd)
+        self._swd_gen = self._swd_gt = None
         if self.kid is not None or self.prc is not None:
             if fid is None:
                 raise ValueError('kid / prc need the FID network: Scorer(fid=InceptionFeatures(...), ...)')
@@ -116,6 +125,11 @@ class Scorer(object):
                 raise ValueError('device uint8 [N,H,W,3] expected, got %s %s on %s' % (t.dtype, tuple(t.shape), t.device))
         if gen_u8.shape != gt_u8.shape:
             raise ValueError('generated %s and ground truth %s differ in shape' % (tuple(gen_u8.shape), tuple(gt_u8.shape)))
+        if self.swd is not None and gen_u8.shape[0]:
+            if self._swd_gen is None:
+                self._swd_gen, self._swd_gt = banks_for(self.swd, gen_u8.device)
+            self._swd_gen.append(gen_u8)
+            self._swd_gt.append(gt_u8)
         self.n += gen_u8.shape[0]
         if self.fid is not None and self.fid_device:
             for b in self._fid_gen.push(gen_u8):
@@ -186,6 +200,9 @@ class Scorer(object):
                 out['kid'], out['kid_std'] = kid_from_features(gen, gt, **self.kid)
             if self.prc is not None:
                 out.update(precision_recall_from_features(gt, gen, **self.prc))
+        if self.swd is not None:
+            value = swd_from_banks(self._swd_gen, self._swd_gt, self.swd['repeats'], self.swd['dirs'], self.swd['seed'])
+            out['swd'], out['swd_levels'] = value['swd'], value['swd_levels']
         into = (list(self._lpips_means), list(self._ssim), list(self._ms_ssim))
         for size, metrics in self._pairs.items():
             bg, bt = self._pair_batches[size]

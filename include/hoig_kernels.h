@@ -1001,6 +1001,62 @@ int hoig_daug_fwd_host(const float *img, const float *cond, const uint32_t *para
 int hoig_daug_bwd(const float *g, const uint32_t *params, float *dimg, int B, int H, int W, int k, float *ws, hoig_stream_t stream);
 int hoig_daug_bwd_host(const float *g, const uint32_t *params, float *dimg, int B, int H, int W, int k, float *ws);
 
+/* ---- LAPLACIAN-PYRAMID SLICED WASSERSTEIN DISTANCE (hoig_amd/csrc/swd.hip, swd.h, swd_host.cpp; hoig_amd/metrics/swd.py;
+ *      docs/swd.md).  A distribution metric between two sets of uint8 images that needs no network.  No floating-point atomics and
+ *      no launch that waits for another workgroup: every sum has one owner and an order fixed by the sizes alone.  Device entries
+ *      never synchronise and allocate nothing; workspaces are 8-byte aligned device memory of at least the stated size.  The *_host
+ *      twins take host memory, make no HIP call and run the same inline functions in the same order: their results are the device's,
+ *      bit for bit.  HOIG_EINVAL, and nothing launched, for a NULL or misaligned pointer, a size out of range or a small workspace. ---- */
+#define HOIG_SWD_K 147             /* floats of a descriptor: a 7 x 7 patch of 3 channels, flattened as (c, dy, dx) */
+#define HOIG_SWD_DEGENERATE 7      /* status bits 1 << c: channel c of hoig_swd_channel_stats_f64 has a zero standard deviation */
+#define HOIG_SORT_NAN 8            /* status bit of hoig_sort_segments_f32: a NaN key was read */
+#define HOIG_SORT_LDS_MAX 2048     /* the longest segment of the sort's single-workgroup LDS route */
+#define HOIG_SORT_TILE 4096        /* keys of a workgroup's tile in the multi-pass route */
+/* floor(log2(min(H, W) / 16)) + 1 (0 below 16): the levels of an H x W image */
+int hoig_swd_levels(int H, int W);
+/* positions [n][L][patches][2] (int32: y0, x0) of the patches of images first_index .. first_index + n - 1 of set `set_id`: the
+ * top-left corner at level l is uniform on [0, (H >> l) - 7] x [0, (W >> l) - 7], drawn as (u32 * range) >> 32 from words 0 and 1
+ * of Philox4x32-10 with key (seed low, seed high) and counter (set id, level, image index low word, patch index). */
+int hoig_swd_positions(uint64_t seed, int set_id, int64_t first_index, int n, int H, int W, int L, int patches, int32_t *positions,
+                       hoig_stream_t stream);
+int hoig_swd_positions_host(uint64_t seed, int set_id, int64_t first_index, int n, int H, int W, int L, int patches, int32_t *positions);
+/* The Gaussian levels 1 .. L - 1 of n images as NHWC fp32 (HOIG_EINVAL for a shape the pyramid does not take: H or W below 16 or
+ * not divisible by 2^(L-1), L above hoig_swd_levels). */
+int64_t hoig_swd_descriptors_workspace_bytes(int n, int H, int W, int L);
+/* out [L][n][patches][147] fp32: the patches of the Laplacian pyramid of u8 [n][H][W][3] at `positions` (clamped into the level).
+ * Filter [1, 4, 6, 4, 1] / 16 as two passes with scipy's 'mirror' boundary; lap[l] = g[l] - up(g[l+1]), lap[L-1] = g[L-1].  The
+ * Gaussian chain goes to the workspace (L - 1 launches, the horizontal pass staged in LDS); the Laplacian levels are never stored:
+ * the gather kernel takes each value from g[l] and at most 3 x 3 values of g[l+1].  L launches. */
+int hoig_swd_descriptors_u8(const uint8_t *u8, int n, int H, int W, int L, int patches, const int32_t *positions, float *out,
+                            void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_swd_descriptors_u8_host(const uint8_t *u8, int n, int H, int W, int L, int patches, const int32_t *positions, float *out);
+/* stats [3][2] doubles = {mean, population standard deviation} of channel c over all 49 * rows values of descriptor rows
+ * [rows][147]: the sum, then sum (x - mean)^2, both fp64 in chunks (swd.h).  status = OR of 1 << c for a zero deviation.  Three
+ * launches. */
+int64_t hoig_swd_channel_stats_workspace_bytes(int64_t rows);
+int hoig_swd_channel_stats_f64(const float *desc, int64_t rows, double *stats, int32_t *status, void *workspace, int64_t workspace_bytes,
+                               hoig_stream_t stream);
+int hoig_swd_channel_stats_f64_host(const float *desc, int64_t rows, double *stats, int32_t *status);
+/* out [D][rows] (direction-major) = the projections of the normalised descriptors on dirs [147][D]: operand
+ * (float)(((double)x - mean_c) / std_c), the sum over k = 0 .. 146 in order by fp32 fused multiply-adds from 0.  64 x 64 tiles, the
+ * operands staged through LDS one channel at a time. */
+int hoig_swd_project_f32(const float *desc, int64_t rows, const double *stats, const float *dirs, int D, float *out, hoig_stream_t stream);
+int hoig_swd_project_f32_host(const float *desc, int64_t rows, const double *stats, const float *dirs, int D, float *out);
+/* Sorts each of the S segments of n fp32 keys (keys [S][n], 4-byte aligned) ascending, in place, as unsigned integers under the
+ * order-preserving map (-0 before +0; a NaN sorts by its bits and sets HOIG_SORT_NAN in *status, which the call clears first).
+ * n <= HOIG_SORT_LDS_MAX: one workgroup per segment, a bitonic network in LDS.  Longer: four passes of an 8-bit LSD radix sort --
+ * per-tile digit counts, a scan per segment, a rank-preserving scatter -- between `keys` and the workspace. */
+int64_t hoig_sort_segments_workspace_bytes(int64_t S, int64_t n);
+int hoig_sort_segments_f32(float *keys, int64_t S, int64_t n, void *workspace, int32_t *status, hoig_stream_t stream);
+int hoig_sort_segments_f32_host(float *keys, int64_t S, int64_t n, int32_t *status);
+int hoig_sort_segments_lds_max(void);
+int hoig_sort_segments_tile(void);
+/* out[0] = sum |a[i] - b[i]|, i in [0, N), in fp64: one partial per workgroup, then one finishing wave.  Two launches. */
+int64_t hoig_swd_sorted_l1_workspace_bytes(int64_t N);
+int hoig_swd_sorted_l1_f64(const float *a, const float *b, int64_t N, double *out, void *workspace, int64_t workspace_bytes,
+                           hoig_stream_t stream);
+int hoig_swd_sorted_l1_f64_host(const float *a, const float *b, int64_t N, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,10 @@ number is the ORACLE AGAINST ITSELF with a different intra-op thread count: the 
 which is all that separates two CPU runs of the reference.  GAN training amplifies that (Adam's first updates have the size of the
 learning rate whatever the gradient's magnitude), so after K steps the floor is far from zero -- that is the "noise" north_star's
 "within noise" refers to.
-    python tools/quality_surrogate.py [--n 256] [--steps 50] [--side 64] [--batch 4] [--save-hip FILE | --load-hip FILE] [--json OUT]"""
+    python tools/quality_surrogate.py [--n 256] [--steps 50] [--side 64] [--batch 4] [--save-hip FILE | --load-hip FILE] [--json OUT]
+--swd (opt-in; the default output is unchanged) adds the Laplacian-pyramid sliced Wasserstein distance (hoig_amd/metrics/swd.py,
+docs/swd.md) of the HIP path's images against the oracle's beside the oracle-against-itself floor: a published distribution metric
+that needs no trained network, one value per pyramid level."""
 import argparse
 import json
 import os
@@ -109,7 +112,20 @@ def compare(a, b, sd_vgg, dims=Q.FEATURE_DIMS):
                 max_rel=float((a - b).abs().max() / b.abs().max()))
 
 
-def report(hip, ora, orb, sd_vgg, log, dims=Q.FEATURE_DIMS):
+def swd_between(a, b):
+    """SWD of two float image sets [N,3,H,W] in [-1, 1] as bytes (the kernels on a GPU, their CPU twins without one): a is the
+    'generated' set (set id 0), b the 'real' one (set id 1)."""
+    from hoig_amd.metrics import swd as S
+    dev = 'cuda' if torch.cuda.is_available() else 'cpu'
+    u8 = lambda x: ((x.float().clamp(-1, 1) + 1.0) * 127.5).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous().to(dev)
+    banks = S.banks_for(S.swd_options(True), dev)
+    banks[0].append(u8(a))
+    banks[1].append(u8(b))
+    out = S.swd_from_banks(banks[0], banks[1])
+    return dict(swd=out['swd'], levels=out['swd_levels'])
+
+
+def report(hip, ora, orb, sd_vgg, log, dims=Q.FEATURE_DIMS, swd=False):
     rows = {}
     fb = lambda x, y: Q.frechet_between(x, y, dims=dims)
     stages = ['init'] + sorted((k for k in ora if k.startswith('k')), key=lambda k: int(k[1:]))
@@ -131,6 +147,11 @@ def report(hip, ora, orb, sd_vgg, log, dims=Q.FEATURE_DIMS):
             % (stage, r['to_real']['hip'], r['to_real']['oracle'], r['to_real']['oracle_other_threads']))
         log('%-8s max |a - b| / max |b| over all images:  HIP vs oracle %.3e | oracle vs oracle %.3e'
             % (stage, r['hip_vs_oracle']['max_rel'], r['oracle_vs_oracle']['max_rel']))
+        if swd:
+            r['swd'] = dict(hip_vs_oracle=swd_between(hip[stage], ora[stage]), oracle_vs_oracle=swd_between(orb[stage], ora[stage]))
+            fmt = lambda v: '%.4f (levels, finest first: %s)' % (v['swd'], ' '.join('%.4f' % x for x in v['levels']))
+            log('%-8s SWD x 1000  HIP vs oracle %s | oracle vs oracle (other thread count) %s'
+                % (stage, fmt(r['swd']['hip_vs_oracle']), fmt(r['swd']['oracle_vs_oracle'])))
     return rows
 
 
@@ -146,6 +167,7 @@ def main():
     ap.add_argument('--oracle-only', action='store_true', help='make the two oracle runs and write them to --oracle-cache (no GPU needed)')
     ap.add_argument('--oracle-cache', default=None, help='file that keeps the two oracle runs (made if absent)')
     ap.add_argument('--load-hip', default=None, help='take the HIP side from a file written by --save-hip (the oracle runs need no GPU)')
+    ap.add_argument('--swd', action='store_true', help='also report the sliced Wasserstein distance of the image sets (docs/swd.md)')
     a = ap.parse_args()
     log = lambda s: print(s, flush=True)
     cores = len(os.sched_getaffinity(0))
@@ -179,7 +201,7 @@ def main():
         if a.oracle_cache:
             torch.save(dict(a=ora, b=orb, args=[a.n, a.steps, a.side, a.batch, ta, tb]), a.oracle_cache)
     sd_vgg = seeded_state(GEN)[3]
-    rows = report(hip, ora, orb, sd_vgg, log)
+    rows = report(hip, ora, orb, sd_vgg, log, swd=a.swd)
     if a.json:
         json.dump(rows, open(a.json, 'w'), indent=1)
 
