@@ -233,6 +233,13 @@ _SIGS = {
     'hoig_sort_segments_tile': [],
     'hoig_swd_sorted_l1_f64': [_vp, _vp, _i64, _vp, _vp, _i64, _vp],
     'hoig_swd_sorted_l1_f64_host': [_vp, _vp, _i64, _vp],
+    'hoig_region_stats_u8': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    'hoig_region_stats_u8_host': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    'hoig_region_boxes': [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    'hoig_region_boxes_host': [_vp, _i, _i, _i, _i, _i, _vp],
+    'hoig_region_tables': [_i, _i, _vp],
+    'hoig_region_crop_resize_u8': [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    'hoig_region_crop_resize_u8_host': [_vp, _i, _i, _i, _vp, _i, _i, _vp],
 }
 
 
@@ -294,6 +301,10 @@ def _load():
     lib.hoig_sort_segments_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_swd_sorted_l1_workspace_bytes.argtypes = [_i64]
     lib.hoig_swd_sorted_l1_workspace_bytes.restype = ctypes.c_int64
+    lib.hoig_region_tables_bytes.argtypes = [_i, _i]
+    lib.hoig_region_tables_bytes.restype = ctypes.c_int64
+    lib.hoig_region_crop_workspace_bytes.argtypes = [_i] * 5
+    lib.hoig_region_crop_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_grad_stats_workspace_bytes.argtypes = [_i64, _i]
     lib.hoig_grad_stats_workspace_bytes.restype = ctypes.c_int64
     lib.hoig_jpeg_decode_workspace_bytes.argtypes = [_vp, _i]
@@ -316,6 +327,7 @@ DAUG_STATE_WORDS, DAUG_MAX_PARTS = 16, 16                # HOIG_DAUG_STATE_WORDS
 SWD_K, SWD_DEGENERATE, SORT_NAN = 147, 7, 8             # HOIG_SWD_K; the status bits HOIG_SWD_DEGENERATE (1 << channel), HOIG_SORT_NAN
 SORT_LDS_MAX = lib.hoig_sort_segments_lds_max()          # HOIG_SORT_LDS_MAX: the longest segment of the sort's LDS route
 SORT_TILE = lib.hoig_sort_segments_tile()                # HOIG_SORT_TILE: keys of a tile of its multi-pass route
+REGION_MAX, REGION_BAD_LABEL = 7, 1                      # HOIG_REGION_MAX; the status bit HOIG_REGION_BAD_LABEL (the label: bits 8 .. 15)
 GUARD_SKIP = 1                                   # HOIG_GUARD_SKIP
 GRAD_CHUNK = lib.hoig_grad_stats_chunk()         # HOIG_GRAD_CHUNK: elements of a stage-1 chunk of hoig_grad_stats
 GRAD_MAX_GRID = lib.hoig_grad_stats_max_grid()   # the most workgroups its stage 1 uses

@@ -6,10 +6,10 @@ mkdir -p _build
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -I../../include -I. -Wno-unused-result -Wno-c++20-designator"
 pids=()
-for f in conv_igemm conv_igemm_bf16 wgrad_igemm_bf16 dgrad_k128 conv_halo16 conv_wino conv_s2_16 wgrad_dma conv_igemm16 conv_flat16 conv_halo5 wgrad_flat conv_head16 conv_f6 conv_small conv_thin norm attn sample pointwise input_prep raster mano data_prep tuning metrics jpeg pil_resize png png_decode fid_stats grad_guard ema d_augment feature_metrics swd; do
-  if [ ! -f _build/$f.o ] || [ $f.hip -nt _build/$f.o ] || [ common.h -nt _build/$f.o ] || [ conv_bf16_common.h -nt _build/$f.o ] || [ conv_m16_common.h -nt _build/$f.o ] || [ tuning.h -nt _build/$f.o ] || [ conv_route.h -nt _build/$f.o ] || [ jpeg_entropy.h -nt _build/$f.o ] || [ jpeg_parallel.h -nt _build/$f.o ] || [ pil_resize.h -nt _build/$f.o ] || [ png_deflate.h -nt _build/$f.o ] || [ png_inflate.h -nt _build/$f.o ] || [ fid_stats.h -nt _build/$f.o ] || [ grad_guard.h -nt _build/$f.o ] || [ ema.h -nt _build/$f.o ] || [ d_augment.h -nt _build/$f.o ] || [ feature_metrics.h -nt _build/$f.o ] || [ swd.h -nt _build/$f.o ] || [ philox.h -nt _build/$f.o ] || [ ../../include/hoig_kernels.h -nt _build/$f.o ]; then
+for f in conv_igemm conv_igemm_bf16 wgrad_igemm_bf16 dgrad_k128 conv_halo16 conv_wino conv_s2_16 wgrad_dma conv_igemm16 conv_flat16 conv_halo5 wgrad_flat conv_head16 conv_f6 conv_small conv_thin norm attn sample pointwise input_prep raster mano data_prep tuning metrics jpeg pil_resize png png_decode fid_stats grad_guard ema d_augment feature_metrics swd region_metrics; do
+  if [ ! -f _build/$f.o ] || [ $f.hip -nt _build/$f.o ] || [ common.h -nt _build/$f.o ] || [ conv_bf16_common.h -nt _build/$f.o ] || [ conv_m16_common.h -nt _build/$f.o ] || [ tuning.h -nt _build/$f.o ] || [ conv_route.h -nt _build/$f.o ] || [ jpeg_entropy.h -nt _build/$f.o ] || [ jpeg_parallel.h -nt _build/$f.o ] || [ pil_resize.h -nt _build/$f.o ] || [ png_deflate.h -nt _build/$f.o ] || [ png_inflate.h -nt _build/$f.o ] || [ fid_stats.h -nt _build/$f.o ] || [ grad_guard.h -nt _build/$f.o ] || [ ema.h -nt _build/$f.o ] || [ d_augment.h -nt _build/$f.o ] || [ feature_metrics.h -nt _build/$f.o ] || [ swd.h -nt _build/$f.o ] || [ region_metrics.h -nt _build/$f.o ] || [ philox.h -nt _build/$f.o ] || [ ../../include/hoig_kernels.h -nt _build/$f.o ]; then
     # input_prep.hip reproduces float->int truncations of the reference: no FMA contraction there (see its header)
-    EXTRA=""; { [ $f = input_prep ] || [ $f = raster ] || [ $f = data_prep ] || [ $f = pil_resize ] || [ $f = fid_stats ] || [ $f = grad_guard ] || [ $f = ema ] || [ $f = d_augment ] || [ $f = feature_metrics ] || [ $f = swd ]; } && EXTRA="-ffp-contract=off"
+    EXTRA=""; { [ $f = input_prep ] || [ $f = raster ] || [ $f = data_prep ] || [ $f = pil_resize ] || [ $f = fid_stats ] || [ $f = grad_guard ] || [ $f = ema ] || [ $f = d_augment ] || [ $f = feature_metrics ] || [ $f = swd ] || [ $f = region_metrics ]; } && EXTRA="-ffp-contract=off"
     $HIPCC $FLAGS $EXTRA -c $f.hip -o _build/$f.o &
     pids+=($!)
   fi
@@ -64,6 +64,11 @@ fi
 # the device
 if [ ! -f _build/swd_host.o ] || [ swd_host.cpp -nt _build/swd_host.o ] || [ swd.h -nt _build/swd_host.o ] || [ philox.h -nt _build/swd_host.o ] || [ ../../include/hoig_kernels.h -nt _build/swd_host.o ]; then
   $HIPCC -x c++ -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. -c swd_host.cpp -o _build/swd_host.o &
+  pids+=($!)
+fi
+# the host half of the region scores (tap tables, workspace size and CPU twins, no HIP call); the tables' doubles round step by step
+if [ ! -f _build/region_metrics_host.o ] || [ region_metrics_host.cpp -nt _build/region_metrics_host.o ] || [ region_metrics.h -nt _build/region_metrics_host.o ] || [ pil_resize.h -nt _build/region_metrics_host.o ] || [ ../../include/hoig_kernels.h -nt _build/region_metrics_host.o ]; then
+  $HIPCC -x c++ -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. -c region_metrics_host.cpp -o _build/region_metrics_host.o &
   pids+=($!)
 fi
 for p in "${pids[@]}"; do wait $p; done

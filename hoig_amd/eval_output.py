@@ -15,6 +15,10 @@ same files from the per-sample device bytes of ``Trainer.eval_images_u8`` (no vi
 ``EvalWriter(..., device_png=True)`` (or ``HOIG_DEVICE_PNG=1``; off by default) lets ``write_images`` encode the sets that arrive as
 device tensors on the device (hoig_amd.png, docs/png_encode.md): the compressed files cross to the host instead of the raw pixels and
 the pool only writes them.  The files decode to the same pixels; their bytes are not Pillow's.
+
+``EvalWriter(..., sav_regions=True)`` (off by default) adds ``<out>/regions/``: ``write_images`` then also takes ``images_u8['regions']``,
+the label maps uint8 [B,H,W] of ``Trainer.eval_regions_u8``, and writes them as 8-bit greyscale PNGs of the label values under the same
+file names -- what ``hoig_amd.metrics.regions.calculate_region_metrics_given_paths`` reads back (docs/region_metrics.md).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -55,8 +59,10 @@ def _save_bytes(data, path):
 class EvalWriter(object):
     """``w = EvalWriter(out_dir, sav_gt=True); w.write(model.get_current_visuals(), batch['nameA'], batch['nameB']); w.close()``"""
 
-    def __init__(self, out_dir, sav_gt=True, side=256, workers=4, device_png=None):
-        self.out_dir, self.side = out_dir, side
+    def __init__(self, out_dir, sav_gt=True, side=256, workers=4, device_png=None, sav_regions=False):
+        self.out_dir, self.side, self.sav_regions = out_dir, side, bool(sav_regions)
+        if self.sav_regions:
+            os.makedirs(os.path.join(out_dir, 'regions'), exist_ok=True)
         self.device_png = os.environ.get('HOIG_DEVICE_PNG', '') == '1' if device_png is None else bool(device_png)
         self.grids = [g for g in GRIDS if sav_gt or g[0] != 'gt']
         for sub, _ in self.grids:                                  # eval.py:47-53
@@ -88,6 +94,15 @@ class EvalWriter(object):
                 raise ValueError('%s: uint8 [B,H,W,C] with B >= %d expected, got %s %s' % (sub, len(names_a), batch.dtype, batch.shape))
             for crop, a, b in zip(batch, names_a, names_b):
                 self._save(crop, os.path.join(self.out_dir, sub, pair_name(a, b)), owned=True)
+        if self.sav_regions:
+            if 'regions' not in images_u8:
+                raise ValueError('sav_regions: images_u8[\'regions\'] (the label maps, uint8 [B,H,W]) is missing')
+            maps = images_u8['regions']
+            maps = maps.cpu().numpy() if hasattr(maps, 'cpu') else np.asarray(maps)
+            if maps.ndim != 3 or maps.dtype != np.uint8 or maps.shape[0] < len(names_a):
+                raise ValueError('regions: uint8 [B,H,W] with B >= %d expected, got %s %s' % (len(names_a), maps.dtype, maps.shape))
+            for lab, a, b in zip(maps, names_a, names_b):
+                self._save(lab, os.path.join(self.out_dir, 'regions', pair_name(a, b)), owned=True)      # (Pillow: mode 'L')
 
     def _write_device(self, sub, batch, names_a, names_b):
         import torch

@@ -1,7 +1,9 @@
 """python -m hoig_amd.metrics {fid,lpips,ssim} PATH1 PATH2: what metrics/pytorch_fid, metrics/lpips.py and metrics/ssim.py print;
 kid, prc: the Kernel Inception Distance and precision / recall / density of PATH1 (generated) against PATH2 (real) on the same
 Inception features (docs/feature_metrics.md); swd: the Laplacian-pyramid sliced Wasserstein distance of PATH1 against PATH2, which
-needs no weights (docs/swd.md)."""
+needs no weights (docs/swd.md); regions: PSNR, MAE and the crop metrics of the hand and the object region of PATH1 (generated) against
+PATH2 (ground truth) with the label maps of --labels (docs/region_metrics.md): SSIM always, LPIPS, FID and KID when their weights are
+given."""
 import argparse
 import os
 import sys
@@ -11,7 +13,7 @@ DIMS = (64, 192, 768, 2048)
 
 def parser():
     p = argparse.ArgumentParser(prog='python -m hoig_amd.metrics', description=__doc__)
-    p.add_argument('metric', choices=('fid', 'lpips', 'ssim', 'kid', 'prc', 'swd'))
+    p.add_argument('metric', choices=('fid', 'lpips', 'ssim', 'kid', 'prc', 'swd', 'regions'))
     p.add_argument('path', nargs=2, help='two image directories (fid: or .npz statistics)')
     p.add_argument('--batch-size', type=int, default=None, help='fid / lpips / kid / prc / swd: 50, ssim: 1 (the reference defaults)')
     p.add_argument('--dims', type=int, default=2048, choices=DIMS, help='fid / kid / prc: Inception feature dimensionality')
@@ -38,7 +40,30 @@ def parser():
     p.add_argument('--swd-dirs', type=int, default=128, help='swd: directions per set')
     p.add_argument('--swd-levels', type=int, default=None, help='swd: at most this many pyramid levels (default: down to 16 pixels)')
     p.add_argument('--swd-seed', type=int, default=0, help='swd: seed of the patch positions and of the directions')
+    p.add_argument('--labels', default=None, help='regions: the directory of label maps (8-bit greyscale: 0 background, 1 hand, 2 object)')
+    p.add_argument('--region-size', type=int, default=128, help='regions: the side of the resized crops')
+    p.add_argument('--region-min-pixels', type=int, default=64, help='regions: a region with fewer pixels does not count')
     return p
+
+
+def _regions(a):
+    """regions: the networks whose weights were given, then one line per value."""
+    from .regions import calculate_region_metrics_given_paths
+    if a.labels is None or not os.path.exists(a.labels):
+        raise RuntimeError('regions needs --labels DIR, got %r' % (a.labels,))
+    fid = lpips = None
+    if a.inception_weights is not None:
+        from .fid import InceptionFeatures
+        fid = InceptionFeatures(a.inception_weights, a.dims, a.precision, a.device)
+    if a.alexnet_weights is not None or a.lpips_weights is not None:
+        from .lpips import LPIPS
+        lpips = LPIPS(a.alexnet_weights, a.lpips_weights, a.precision, a.device)
+    kid = dict(subsets=a.kid_subsets, subset_size=a.kid_subset_size, seed=a.kid_seed) if fid is not None else None
+    v = calculate_region_metrics_given_paths(a.path, a.labels, a.region_size, a.region_min_pixels, a.batch_size or 50, fid, lpips, True,
+                                             kid, a.device, fid_device=bool(a.device_fid))
+    for key, value in v.items():
+        print('%s:  %r' % (key, value))
+    return v
 
 
 def main(argv=None):
@@ -48,6 +73,8 @@ def main(argv=None):
     for p in a.path:
         if not os.path.exists(p):
             raise RuntimeError('Invalid path: %s' % p)
+    if a.metric == 'regions':
+        return _regions(a)
     if a.metric == 'fid':
         from .fid import calculate_fid_given_paths
         v = calculate_fid_given_paths(a.path, a.batch_size or 50, a.device, a.dims, a.inception_weights, a.precision,

@@ -16,6 +16,7 @@ from . import kernels as K
 from .fid import calculate_frechet_distance, compute_statistics_of_path
 from .feature_metrics import FeatureBank, _options, kid_from_features, precision_recall_from_features
 from .fid_device import Moments, fid_device_option, frechet_distance_device
+from .regions import RegionScores, region_options
 from .ssim import ssim_pairs_u8
 from .swd import banks_for, swd_from_banks, swd_options
 
@@ -62,10 +63,16 @@ class Scorer(object):
     between the two streams (swd.py, docs/swd.md).  It needs no network -- Scorer(fid=None, lpips=None, ssim=False, swd=True) runs
     without any weights.  update() keeps each image's patch descriptors on the device (swd.SWDBank, 4 * 147 * patches * levels bytes
     per image and stream) and result() gains 'swd' and 'swd_levels', equal to calculate_swd_given_paths on the directories whatever
-    the sizes of the update() calls."""
+    the sizes of the update() calls.
+
+    regions (off by default; True, or a dict of size, min_pixels, batch): scores on the hand and the object region (regions.py,
+    docs/region_metrics.md).  update() then takes a third argument, the ground truth's label map as device uint8 [N,H,W] (0 background,
+    1 hand, 2 object: Trainer.eval_regions_u8), and result() gains 'psnr', 'mae' of the whole frame and per region r in ('hand',
+    'object') 'n_<r>', 'psnr_<r>', 'mae_<r>' and -- from square crops around the region, for the metrics this scorer has --
+    'lpips_<r>', 'ssim_<r>', 'fid_<r>', 'kid_<r>', 'kid_std_<r>'.  It takes no fid_reference, prc or swd per region."""
 
     def __init__(self, fid=None, lpips=None, ssim=True, img_size=256, fid_batch=50, lpips_batch=50, ssim_batch=50, fid_reference=None,
-                 fid_device=None, kid=None, prc=None, swd=None):
+                 fid_device=None, kid=None, prc=None, swd=None, regions=None):
         self.fid, self.lpips, self.ssim, self.img_size = fid, lpips, bool(ssim), img_size
         self.n = 0
         if isinstance(fid_reference, str):
@@ -98,6 +105,10 @@ class Scorer(object):
             self._pairs.setdefault(ssim_batch, []).append('ssim')
         self._pair_batches = {size: (_Batches(size), _Batches(size)) for size in self._pairs}
         self._lpips_means, self._ssim, self._ms_ssim = [], [], []
+        self.regions = region_options(regions)
+        self._regions = None
+        if self.regions is not None:
+            self._regions = RegionScores(self.regions, fid, lpips, self.ssim, self.kid, self.fid_device)
 
     # ---- one batch, as the path functions run it
     def _features_device(self, u8, bank=None):
@@ -119,12 +130,19 @@ class Scorer(object):
             into[1].append(s)
             into[2].append(m)
 
-    def update(self, gen_u8, gt_u8):
+    def update(self, gen_u8, gt_u8, regions_u8=None):
+        if (regions_u8 is None) != (self._regions is None):
+            raise ValueError('update(gen_u8, gt_u8, regions_u8): the label map goes with Scorer(regions=...), and only with it')
         for t in (gen_u8, gt_u8):
             if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 4 or t.shape[-1] != 3:
                 raise ValueError('device uint8 [N,H,W,3] expected, got %s %s on %s' % (t.dtype, tuple(t.shape), t.device))
         if gen_u8.shape != gt_u8.shape:
             raise ValueError('generated %s and ground truth %s differ in shape' % (tuple(gen_u8.shape), tuple(gt_u8.shape)))
+        if self._regions is not None:
+            if regions_u8.dtype != torch.uint8 or not regions_u8.is_cuda or tuple(regions_u8.shape) != tuple(gen_u8.shape[:3]):
+                raise ValueError('regions_u8: device uint8 %s expected, got %s %s on %s' % (tuple(gen_u8.shape[:3]), regions_u8.dtype,
+                                                                                        tuple(regions_u8.shape), regions_u8.device))
+            self._regions.update(gen_u8, gt_u8, regions_u8)
         if self.swd is not None and gen_u8.shape[0]:
             if self._swd_gen is None:
                 self._swd_gen, self._swd_gt = banks_for(self.swd, gen_u8.device)
@@ -213,19 +231,29 @@ class Scorer(object):
         if self.ssim:
             out['ssim'] = torch.cat(into[1]).double().mean().item()
             out['ms_ssim'] = torch.cat(into[2]).double().mean().item()
+        if self._regions is not None:
+            out.update(self._regions.result())
         return out
 
 
 def score_model(model, dataset, scorer, writer=None):
     """The evaluation loop without files: for every batch of `dataset` (dicts as eval.py's loader yields them) forward() under
     no_grad, the three images as device bytes, scorer.update(imitators, gt) and, with an EvalWriter, the PNGs of the same bytes.
+    A scorer with regions also takes model.eval_regions_u8(), and a writer with sav_regions keeps those label maps as PNGs.
     Returns scorer.result()."""
+    with_regions = getattr(scorer, 'regions', None) is not None
     for batch in dataset:
         model.set_input(batch)
         with torch.no_grad():
             outs = model.forward()
         images = model.eval_images_u8(outs)
-        scorer.update(images['imitators'], images['gt'])
+        if with_regions:
+            labels = model.eval_regions_u8()
+            scorer.update(images['imitators'], images['gt'], labels)
+            if writer is not None and getattr(writer, 'sav_regions', False):
+                images = dict(images, regions=labels)
+        else:
+            scorer.update(images['imitators'], images['gt'])
         if writer is not None:
             writer.write_images(images, batch['nameA'], batch['nameB'])
     return scorer.result()

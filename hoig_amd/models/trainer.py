@@ -843,6 +843,15 @@ class Trainer(BaseModel):
         return OrderedDict([('source', ops.tensor2im_nhwc_u8(n['real_src'])), ('imitators', ops.tensor2im_nhwc_u8(fake_tsf)),
                             ('gt', ops.tensor2im_nhwc_u8(n['real_tsf']))])
 
+    def eval_regions_u8(self):
+        """The label map of the current batch's target view, device uint8 [B,H,W]: 1 (hand) where hand_mask < 0.5 -- that mask is 1
+        OUTSIDE the hand --, else 2 (object) where bg_mask < 0.5, else 0: what hoig_amd.metrics.stream.Scorer(regions=...) takes
+        beside eval_images_u8's bytes (docs/region_metrics.md)."""
+        n = self._n
+        B = n['real_tsf'].shape[0]
+        from ..metrics.regions import labels_from_masks
+        return labels_from_masks(n['bg_mask'][B:, :, :, 0], n['hand_mask'][B:, :, :, 0])     # (source view first, then the target)
+
     @staticmethod
     def _im(x_nhwc, idx=0, unnormalize=True):
         """utils/util.py:249-264 tensor2im: CHW uint8 of sample `idx`, or of the padding-0 grid when idx < 0."""

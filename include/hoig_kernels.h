@@ -1057,6 +1057,46 @@ int hoig_swd_sorted_l1_f64(const float *a, const float *b, int64_t N, double *ou
                            hoig_stream_t stream);
 int hoig_swd_sorted_l1_f64_host(const float *a, const float *b, int64_t N, double *out);
 
+/* ---- REGION SCORES: MASKED PSNR / MAE SUMS AND SQUARE CROPS OF LABELLED REGIONS (hoig_amd/csrc/region_metrics.hip,
+ *      region_metrics.h, region_metrics_host.cpp; hoig_amd/metrics/regions.py; docs/region_metrics.md).  A label map is uint8
+ *      [N][H][W]: 0 background, r in 1 .. R region r.  Every quantity is an integer or a byte, so no result depends on the order
+ *      of a sum.  Device entries never synchronise and allocate nothing; the *_host twins take host memory, make no HIP call and
+ *      run the same inline functions.  HOIG_EINVAL, and nothing launched, for a NULL or misaligned pointer, H or W outside
+ *      1 .. 4096, R outside 1 .. HOIG_REGION_MAX, S outside HOIG_REGION_MIN_SIZE .. HOIG_REGION_MAX_SIZE. ---- */
+#define HOIG_REGION_MAX 7          /* the most regions (label values 1 .. 7) */
+#define HOIG_REGION_ROW 8          /* int64 of a statistics row */
+#define HOIG_REGION_MIN_SIZE 4     /* the range of a crop's output side S */
+#define HOIG_REGION_MAX_SIZE 512
+#define HOIG_REGION_BAD_LABEL 1    /* status bit 0: a label above R was read; bits 8 .. 15 then hold the largest such label */
+/* stats [N][R + 1][8] int64, row = [count, sum |d|, sum d^2, x0, y0, x1, y1, 0] with d = gen - gt per channel, summed over the 3
+ * channels of the row's pixels; (x0, y0, x1, y1) their inclusive bounding box, (W, H, -1, -1) for an empty row.  Row 0: every
+ * pixel of the image; row r: the pixels labelled r.  A label above R counts in row 0 only and sets *status (above).  One pass over
+ * gen, gt [N][H][W][3] and labels: per-lane integer partials, a sum per workgroup, then integer atomics on `stats` (add, min,
+ * max), which the entry initialises together with *status in a launch of its own.  8-byte aligned stats, 4-byte aligned status. */
+int hoig_region_stats_u8(const uint8_t *gen, const uint8_t *gt, const uint8_t *labels, int N, int H, int W, int R, int64_t *stats,
+                         int32_t *status, hoig_stream_t stream);
+int hoig_region_stats_u8_host(const uint8_t *gen, const uint8_t *gt, const uint8_t *labels, int N, int H, int W, int R, int64_t *stats,
+                              int32_t *status);
+/* boxes [N][R][4] int32 = [left, top, side, valid] from the rows 1 .. R of `stats`: side0 = max(x1 - x0 + 1, y1 - y0 + 1),
+ * pad = (side0 + 3) / 4, side = min(side0 + 2 pad, H, W), left = clamp(floor((x0 + x1 + 1 - side) / 2), 0, W - side), top likewise
+ * with y and H, valid = count >= max(min_pixels, 1); an invalid box is (0, 0, 0, 0).  Square and inside the image. */
+int hoig_region_boxes(const int64_t *stats, int N, int H, int W, int R, int min_pixels, int32_t *boxes, hoig_stream_t stream);
+int hoig_region_boxes_host(const int64_t *stats, int N, int H, int W, int R, int min_pixels, int32_t *boxes);
+/* The taps of Pillow's 8-bit BILINEAR resize (hoig_pil_bilinear_table) of every source side 1 .. max_side to S, in one int32
+ * buffer: [max_side, S], then (offset, ksize) of side s at words 2 s and 2 s + 1, then the tables; offsets count int32 from the
+ * start.  hoig_region_tables fills host memory of hoig_region_tables_bytes bytes. */
+int64_t hoig_region_tables_bytes(int max_side, int S);
+int hoig_region_tables(int max_side, int S, int32_t *tables);
+/* dst [R][N][S][S][3]: crop (r, n) is the window (left, top, side) of boxes [N][R][4] in image n of src [N][H][W][3], resized to
+ * S x S as Image.crop(box).resize((S, S), Image.BILINEAR) does it, equal in every byte (taps never reach outside the window); an
+ * invalid box, or one that is not inside the image or the tables, gives zeros.  `tables`: hoig_region_tables(min(H, W), S) in
+ * device memory.  Two launches: along x into the workspace (a grid sized for side = min(H, W), each workgroup reads its box and
+ * leaves when it has nothing to do), then along y.  4-byte aligned dst and workspace. */
+int64_t hoig_region_crop_workspace_bytes(int N, int H, int W, int R, int S);
+int hoig_region_crop_resize_u8(const uint8_t *src, int N, int H, int W, const int32_t *boxes, int R, int S, const int32_t *tables,
+                               uint8_t *dst, void *workspace, hoig_stream_t stream);
+int hoig_region_crop_resize_u8_host(const uint8_t *src, int N, int H, int W, const int32_t *boxes, int R, int S, uint8_t *dst);
+
 #ifdef __cplusplus
 }
 #endif
