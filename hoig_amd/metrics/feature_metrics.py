@@ -10,16 +10,11 @@ in, over k.  ``FeatureBank`` keeps the fp32 blocks InceptionFeatures.features_u8
 Every product is made by the fp64 kernels of hoig_amd/csrc/feature_metrics.hip; nothing of size m x m or n x n is stored.  CUDA
 tensors go to the kernels, CPU tensors to their host twins, which walk the same code.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib as L
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .._twin import ptr as _p, run as _run
 
 
 def _features(x, name):
@@ -28,21 +23,6 @@ def _features(x, name):
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError('%s: fp32 [N, dims] expected, got %s %s' % (name, x.dtype, tuple(x.shape)))
     return x.detach().contiguous()
-
-
-def _run(name, ref, args, workspace_bytes=None):
-    """The device entry on `ref`'s stream with its workspace, or the host twin for a CPU tensor."""
-    if not ref.is_cuda:
-        L.call(name + '_host', *args)
-        return
-    with torch.cuda.device(ref.device):
-        tail = ()
-        if workspace_bytes is not None:
-            if workspace_bytes < 0:
-                raise ValueError('%s: no workspace for these sizes' % name)
-            ws = torch.empty((workspace_bytes + 7) // 8 + 1, dtype=torch.float64, device=ref.device)
-            tail = (_p(ws), workspace_bytes)
-        L.call(name, *(tuple(args) + tail + (torch.cuda.current_stream().cuda_stream,)))
 
 
 def _status_error(what, status):

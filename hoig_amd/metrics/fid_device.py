@@ -13,13 +13,13 @@ returns the value of the formula itself.
 Every function here runs on the tensors' own device: CUDA tensors go to the kernels, CPU tensors to their host twins
 (``frechet_distance_host_twin``, ``Moments(dims, 'cpu')``), which walk the same code.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
 from .. import _lib as L
+from .._twin import ptr as _p, run as _run
 
 
 def fid_device_option(value):
@@ -27,24 +27,11 @@ def fid_device_option(value):
     return os.environ.get('HOIG_DEVICE_FID', '') == '1' if value is None else bool(value)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _ld(t):
     """Leading dimension of a 2-D tensor whose rows are contiguous (a column slice of a larger matrix included)."""
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError('a matrix with contiguous rows expected, got shape %s strides %s' % (tuple(t.shape), t.stride()))
     return t.stride(0) if t.shape[0] > 1 and t.stride(0) >= t.shape[1] else t.shape[1]
-
-
-def _run(name, ref, args, tail=()):
-    """The device entry on `ref`'s stream, or its host twin for a CPU tensor."""
-    if ref.is_cuda:
-        with torch.cuda.device(ref.device):
-            L.call(name, *(tuple(args) + tuple(tail) + (torch.cuda.current_stream().cuda_stream,)))
-    else:
-        L.call(name + '_host', *args)
 
 
 def gemm_tn(a, b, c, flags=0, pivot=None):
@@ -72,7 +59,7 @@ def pivoted_cholesky(sigma):
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         tail = (_p(ws), nbytes)
     try:
-        _run('hoig_pchol_f64', sigma, (_p(sigma), _ld(sigma), D, _p(fac), D, _p(piv), _p(info)), tail)
+        _run('hoig_pchol_f64', sigma, (_p(sigma), _ld(sigma), D, _p(fac), D, _p(piv), _p(info)), tail=tail)
     except L.HoigKernelError:
         if sigma.is_cuda or int(info[1]) == 0:
             raise                         # (the twin also returns the status it writes)
@@ -92,7 +79,7 @@ def sym_eigvals(a):
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
         tail = (_p(ws), nbytes)
     try:
-        _run('hoig_sym_eigvals_f64', a, (_p(a), _ld(a), n, _p(lam), _p(info)), tail)
+        _run('hoig_sym_eigvals_f64', a, (_p(a), _ld(a), n, _p(lam), _p(info)), tail=tail)
     except L.HoigKernelError:
         if a.is_cuda or int(info[0]) == 0:
             raise

@@ -14,23 +14,12 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .._twin import ptr as _p, run as _run
 from .feature_metrics import FeatureBank, _options, kid_from_features
 
 NAMES = ('hand', 'object')
 DEFAULTS = dict(size=128, min_pixels=64, batch=50)
 SSIM_WINDOW = 11
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _run(name, ref, args):
-    if not ref.is_cuda:
-        L.call(name + '_host', *args)
-        return
-    with torch.cuda.device(ref.device):
-        L.call(name, *(tuple(args) + (torch.cuda.current_stream().cuda_stream,)))
 
 
 def region_options(value):

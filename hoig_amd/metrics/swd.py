@@ -9,37 +9,18 @@ first, and their mean.
 Every stage is a kernel of hoig_amd/csrc/swd.hip; CUDA tensors go to the kernels, CPU tensors to their host twins, which run the same
 code in the same order and give the same bits.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
 from .. import _lib as L
+from .._twin import ptr as _p, run as _run
 from .feature_metrics import _options  # noqa: F401  (the Scorer's swd= argument is read like kid= and prc=)
 
 K = L.SWD_K
 DEFAULTS = dict(patches=128, repeats=4, dirs=128, levels=None, seed=0)
 SET_GEN, SET_REAL = 0, 1
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _run(name, ref, args, workspace_bytes=None):
-    """The device entry on `ref`'s stream (with its workspace), or the host twin for a CPU tensor."""
-    if not ref.is_cuda:
-        L.call(name + '_host', *args)
-        return
-    with torch.cuda.device(ref.device):
-        ws = ()
-        if workspace_bytes is not None:
-            if workspace_bytes < 0:
-                raise ValueError('%s: no workspace for these sizes' % name)
-            buf = torch.empty((workspace_bytes + 7) // 8 + 1, dtype=torch.float64, device=ref.device)
-            ws = (_p(buf), workspace_bytes)
-        L.call(name, *(tuple(args) + ws + (torch.cuda.current_stream().cuda_stream,)))
 
 
 # ------------------------------------------------------------------------------------------------ the pyramid and its patches

@@ -1174,8 +1174,12 @@ def _conv_dgrad_raw(d, g, w, dx, transposed=False, addend=None):
 #   _conv_fwd_raw, _conv_dgrad_raw                tools/conv_table.py (times each launch)
 def _reexport():
     import importlib
+    import sys
     g = globals()
     for mod in ('ops_norm', 'ops_small', 'ops_attn', 'ops_loss', 'ops_daug'):
+        if __package__ + '.' + mod in sys.modules:       # a family that is being imported right now has no names to hand over yet
+            raise ImportError('import hoig_amd.ops first: it was reached from the import of hoig_amd.%s, whose names it '
+                              're-exports and which is not complete yet' % mod)
         m = importlib.import_module('.' + mod, __package__)
         for k, v in vars(m).items():
             if not k.startswith('__') and k not in ('_o', 'L', 'ConvDesc', 'Function', 'torch', 'contextlib'):
