@@ -82,6 +82,8 @@ class Trainer(BaseModel):
     _ema = None               # (class defaults: a model assembled without __init__, as bench.py's forward leg is, keeps no average)
     _eval_ema = False
     _daug = None              # (likewise: no discriminator augmentation)
+    _gan = None               # (likewise: the least-squares objective ...)
+    _lecam = None             # (... without the LeCam regulariser)
 
     def __init__(self, opt, use_ddp=False):
         super(Trainer, self).__init__(opt, use_ddp)
@@ -129,6 +131,12 @@ class Trainer(BaseModel):
         from ..d_augment import parse_options as parse_daug_options
         self._daug_options = parse_daug_options(opt)
         self._daug = None                # DAugment; None with the option off, and in an eval-only model
+        # the adversarial objective (docs/gan_objectives.md): opt.gan_mode / HOIG_GAN_MODE = 'lsgan' (the reference's, the default) |
+        # 'hinge' | 'logistic'; opt.lecam / HOIG_LECAM > 0: the LeCam regulariser on D, with opt.lecam_decay, lecam_start, lecam_form
+        from ..gan_loss import parse_options as parse_gan_options, active as gan_active
+        self._gan_options = parse_gan_options(opt)
+        self._gan = self._gan_options if gan_active(self._gan_options) else None     # None: the least-squares path, launch for launch
+        self._lecam = None               # LeCam; None with the regulariser off, and in an eval-only model
 
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
@@ -219,6 +227,13 @@ class Trainer(BaseModel):
                                  '(give a fixed d_augment_p)')
             rank = dist.get_rank() if (self._use_ddp and dist.is_initialized()) else 0
             self._daug = DAugment(self.device, rank=rank, batch=getattr(self._opt, 'batch_size', None), **self._daug_options)
+        if self._gan is not None and self._gan['lecam'] > 0.0:
+            from ..gan_loss import LeCam
+            if self._sync_active():
+                raise ValueError("lecam %r under an active gradient exchange: the ranks' anchors would drift apart (leave lecam at 0; "
+                                 "gan_mode 'hinge' / 'logistic' keep no state and are fine)" % (self._gan['lecam'],))
+            g = self._gan
+            self._lecam = LeCam(self.device, g['lecam'], decay=g['decay'], start=g['start'], form=g['form'])
 
     def _init_prefetch_inputs(self):
         self._real_src = self._real_tsf = self._bg_mask = self._hand_mask = None
@@ -255,7 +270,7 @@ class Trainer(BaseModel):
             self._crt_tsf = VGGLoss(vgg=vgg_net)
         # the terms of the two objectives live in device slots that the loss kernels add into (ops.LossSlots)
         self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth'], self.device)
-        self._d_terms = ops.LossSlots(['d'], self.device, extra=['d_real', 'd_fake'])
+        self._d_terms = ops.LossSlots(['d'], self.device, extra=['d_real', 'd_fake'] + (['d_reg'] if self._lecam is not None else []))
         z = lambda: torch.zeros((), device=self.device)
         self._loss_g_rec, self._loss_g_tsf, self._loss_g_adv = z(), z(), z()
         self._loss_g_smooth, self._loss_g_mask, self._loss_g_mask_smooth = z(), z(), z()
@@ -720,13 +735,13 @@ class Trainer(BaseModel):
                 self._wait_d()
                 d_fake = self._D.forward_nhwc(self._d_fake_in(fake_tsf))
                 d_fake = ops.delay_backward(d_fake, 'loss_adv')
-                self._loss_g_adv = ops.lsgan_loss(d_fake, 0.0, o.lambda_D_prob, into=into('g_adv'))
+                self._loss_g_adv = self._g_adv_loss(d_fake, into('g_adv'))
             ops.cross_stream(fake_tsf, s_adv)
         else:
             s_vgg = None
             self._wait_d()
             d_fake = self._D.forward_nhwc(self._d_fake_in(fake_tsf))
-            self._loss_g_adv = ops.lsgan_loss(d_fake, 0.0, o.lambda_D_prob, into=into('g_adv'))
+            self._loss_g_adv = self._g_adv_loss(d_fake, into('g_adv'))
         self._loss_g_rec = ops.l1_loss(fake_src, n['real_src'], o.lambda_rec, into=into('g_rec'))
         # the reference uses self._crt_tsf in both branches of `if use_vgg` (:443-446); it only exists with --use_vgg
         tsf = self._crt_tsf.forward_nhwc(fake_tsf, n['real_tsf'], o.lambda_tsf, side=s_vgg, into=into('g_tsf'))
@@ -742,6 +757,13 @@ class Trainer(BaseModel):
         self._loss_g_tsf, self._loss_g_mask = T.value('g_tsf'), T.value('g_mask')
         self._loss_g_mask_smooth = T.value('g_mask_smooth')
         return T.total(self._loss_g_adv, self._loss_g_rec, *(tsf + masks + smooth))
+
+    def _g_adv_loss(self, d_fake, into):
+        """g_adv on D(fake): the reference's least-squares term against 0, or the generator's term of gan_mode (never a LeCam term)."""
+        if self._gan is None or self._gan['mode'] == _lib.GAN_LSGAN:
+            return ops.lsgan_loss(d_fake, 0.0, self._opt.lambda_D_prob, into=into)
+        from ..gan_loss import gan_g_loss
+        return gan_g_loss(d_fake, self._gan['mode'], self._opt.lambda_D_prob, into)
 
     def _d_fake_in(self, fake_tsf):
         """D's input in the G loss: [fake | cond], under the records `_phase_g` drew for this step when D's inputs are augmented."""
@@ -777,6 +799,14 @@ class Trainer(BaseModel):
             self._daug.adapt(d_real.detach())
         T = self._d_terms
         T.begin()
+        if self._gan is not None:
+            # one fused head in place of the four launches below: the objective of gan_mode, the LeCam term and its tick, both means
+            from ..gan_loss import gan_d_loss
+            reg = T.term('d_reg') if self._lecam is not None else None
+            loss = gan_d_loss(d_real, d_fake, self._gan['mode'], o.lambda_D_prob, T.term('d'), lecam=self._lecam,
+                              into_real=T.term('d_real'), into_fake=T.term('d_fake'), into_reg=reg)
+            self._d_real, self._d_fake = T.value('d_real'), T.value('d_fake')
+            return T.total(loss)
         loss_real = ops.lsgan_loss(d_real, 1.0, o.lambda_D_prob, into=T.term('d'))
         loss_fake = ops.lsgan_loss(d_fake, -1.0, o.lambda_D_prob, into=T.term('d'))
         with torch.no_grad():
@@ -812,6 +842,11 @@ class Trainer(BaseModel):
             out['d_aug_p'] = r['p']
             if self._daug.adaptive:
                 out['d_aug_rt'] = r['rt']
+        if self._lecam is not None:                   # (likewise: LeCam.report() copies to the host)
+            r = self._lecam.report()
+            out['lecam_real'], out['lecam_fake'] = r['real'], r['fake']
+            out['d_reg'] = self._d_terms.value('d_reg').item()
+            out['lecam_bad'] = r['bad']
         return out
 
     def grad_report(self):
@@ -920,6 +955,8 @@ class Trainer(BaseModel):
             self._ckpt.write(dict(updates=self._ema.updates(), decay=self._ema.decay, warmup=self._ema.warmup), 'opt', label, 'G_ema')
         if self._daug is not None:
             self._ckpt.write(self._daug.state_dict(), 'opt', label, 'D_aug')
+        if self._lecam is not None:
+            self._ckpt.write(self._lecam.state_dict(), 'opt', label, 'D_lecam')
 
     def load(self):
         """HOIG_HOv3/models/trainer.py:562-575; the HOIG_DexYCB copy (its trainer.py:558-573) differs twice: it hands the file's
@@ -945,6 +982,21 @@ class Trainer(BaseModel):
                 self._load_ema(load_epoch)
             if self._daug is not None:
                 self._load_daug(load_epoch)
+            if self._lecam is not None:
+                self._load_lecam(load_epoch)
+
+    def _load_lecam(self, load_epoch):
+        quiet = dist.is_available() and dist.is_initialized() and dist.get_rank() != 0
+        path = self._ckpt.file('opt', load_epoch, 'D_lecam')
+        if not os.path.isfile(path):
+            self._lecam.reset()
+            if not quiet:
+                print('no LeCam checkpoint %s: no tick taken, the anchors start from the first step' % path)
+            return
+        sd = self._ckpt.read(path)
+        self._lecam.load_state_dict(sd)
+        if not quiet:
+            print('loaded LeCam state: %s (%d ticks, anchors %g / %g)' % (path, sd['count'], sd['alpha_real'], sd['alpha_fake']))
 
     def _load_daug(self, load_epoch):
         quiet = dist.is_available() and dist.is_initialized() and dist.get_rank() != 0

@@ -1097,6 +1097,46 @@ int hoig_region_crop_resize_u8(const uint8_t *src, int N, int H, int W, const in
                                uint8_t *dst, void *workspace, hoig_stream_t stream);
 int hoig_region_crop_resize_u8_host(const uint8_t *src, int N, int H, int W, const int32_t *boxes, int R, int S, uint8_t *dst);
 
+/* ---- OPT-IN GAN OBJECTIVES AND THE LECAM REGULARISER (hoig_amd/csrc/gan_loss.hip, gan_loss.h, gan_loss_host.cpp;
+ *      hoig_amd/gan_loss.py; docs/gan_objectives.md).  One pass over D's logits gives the objective, its pre-scaled gradients, the
+ *      report means and the regulariser; every sum is fp64 in an order fixed by the two sizes (no floating-point atomics, no wait
+ *      between workgroups); the LeCam anchors live in a device state that the same call ticks.  The *_host twins take host memory, make
+ *      no HIP call and run the same inline functions in the same order: outside HOIG_GAN_LOGISTIC their results are the device's, bit
+ *      for bit.  Every entry point returns HOIG_EINVAL, and launches nothing, for an unknown mode or form, a non-positive count, a
+ *      negative or non-finite weight, a misaligned pointer (state, workspace: 8 bytes; floats: 4), a missing logit pointer, a short
+ *      workspace, or a gradient that overlaps the other side's logits or gradient. ---- */
+#define HOIG_GAN_LSGAN 0           /* D: s mean((a - 1)^2) + s mean((b + 1)^2);          G: s mean(b^2) */
+#define HOIG_GAN_HINGE 1           /* D: s mean(max(0, 1 - a)) + s mean(max(0, 1 + b));  G: -s mean(b) */
+#define HOIG_GAN_LOGISTIC 2        /* D: s mean(softplus(-a)) + s mean(softplus(b));     G: s mean(softplus(-b)) */
+#define HOIG_LECAM_PAPER 0         /* R = mean((a - alpha_F)^2) + mean((b - alpha_R)^2) */
+#define HOIG_LECAM_RELU 1          /* R = mean(max(0, a - alpha_F)^2) + mean(max(0, alpha_R - b)^2) */
+#define HOIG_LECAM_STATE_WORDS 8   /* 64-bit words of the state (layout: gan_loss.h, docs/gan_objectives.md) */
+#define HOIG_GAN_THREADS 256       /* threads of a workgroup */
+#define HOIG_GAN_CHUNK 512         /* logits of a chunk: a workgroup takes whole chunks */
+#define HOIG_GAN_MAX_GRID 64       /* the most workgroups: with more chunks than this a workgroup walks several */
+/* The D head.  a[0 .. n_a): D(real), b[0 .. n_b): D(fake), fp32; s: the objective's weight; state: the LeCam state (device memory,
+ * HOIG_LECAM_STATE_WORDS words) or NULL for no regulariser.  With w = 1 when the state's tick count, as it stands before the call, has
+ * reached its start word, else 0:
+ *   da[i] = (float)(s / n_a) f_a'(a[i]) + (float)(w lambda_lc / n_a) r_a'(a[i]),   db likewise   (either may be NULL: not written)
+ *   *term   += (float)(s mean f_a(a) + s mean f_b(b) + lambda_lc w R)
+ *   *mean_a += (float)mean(a),  *mean_b += (float)mean(b),  *reg += (float)(w R)                 (each may be NULL)
+ * and then the state takes its tick: alpha_R <- gamma alpha_R + (1 - gamma) mean(a), alpha_F likewise with mean(b) (the first tick
+ * sets them to the means), count + 1 -- or, when a mean is not finite, only the state's refusal counter + 1.  The regulariser reads
+ * the anchors as they stood before the call.  Two launches on `stream`; never synchronises, allocates nothing.  workspace: device
+ * memory of hoig_gan_d_loss_workspace_bytes(n_a, n_b) bytes (< 0: invalid sizes). */
+int64_t hoig_gan_d_loss_workspace_bytes(int64_t n_a, int64_t n_b);
+int hoig_gan_d_loss(int mode, const float *a, int64_t n_a, const float *b, int64_t n_b, double s, double lambda_lc, int lecam_form,
+                    uint64_t *state, float *da, float *db, float *term, float *mean_a, float *mean_b, float *reg, void *workspace,
+                    int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_gan_d_loss_host(int mode, const float *a, int64_t n_a, const float *b, int64_t n_b, double s, double lambda_lc, int lecam_form,
+                         uint64_t *state, float *da, float *db, float *term, float *mean_a, float *mean_b, float *reg);
+/* The G head: db[i] = (float)(s / n_b) g'(b[i]) (or NULL) and *term += (float)(s mean g(b)) for the mode's generator term g.  No
+ * state: the generator's objective has no LeCam term. */
+int64_t hoig_gan_g_loss_workspace_bytes(int64_t n_b);
+int hoig_gan_g_loss(int mode, const float *b, int64_t n_b, double s, float *db, float *term, void *workspace, int64_t workspace_bytes,
+                    hoig_stream_t stream);
+int hoig_gan_g_loss_host(int mode, const float *b, int64_t n_b, double s, float *db, float *term);
+
 #ifdef __cplusplus
 }
 #endif
