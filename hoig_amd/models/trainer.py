@@ -84,6 +84,7 @@ class Trainer(BaseModel):
     _daug = None              # (likewise: no discriminator augmentation)
     _gan = None               # (likewise: the least-squares objective ...)
     _lecam = None             # (... without the LeCam regulariser)
+    _region = None            # (likewise: no region reconstruction terms)
 
     def __init__(self, opt, use_ddp=False):
         super(Trainer, self).__init__(opt, use_ddp)
@@ -137,6 +138,12 @@ class Trainer(BaseModel):
         self._gan_options = parse_gan_options(opt)
         self._gan = self._gan_options if gan_active(self._gan_options) else None     # None: the least-squares path, launch for launch
         self._lecam = None               # LeCam; None with the regulariser off, and in an eval-only model
+        # the region reconstruction terms of G (docs/region_loss.md), off by default: opt.lambda_rec_hand / HOIG_LAMBDA_REC_HAND and
+        # opt.lambda_rec_obj / HOIG_LAMBDA_REC_OBJ > 0 weight an L1 term on the hand's and the object's pixels, each normalised by
+        # its own pixel count; opt.region_loss_views ('both' | 'src' | 'tsf'), opt.region_loss_min_pixels (64)
+        from ..region_loss import parse_options as parse_region_options, active as region_active
+        self._region_options = parse_region_options(opt)
+        self._region = self._region_options if region_active(self._region_options) else None   # None: ops.l1_loss, launch for launch
 
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
@@ -269,7 +276,11 @@ class Trainer(BaseModel):
         if self._opt.use_vgg:
             self._crt_tsf = VGGLoss(vgg=vgg_net)
         # the terms of the two objectives live in device slots that the loss kernels add into (ops.LossSlots)
-        self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth'], self.device)
+        if self._region is None:
+            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth'], self.device)
+        else:       # (the report slots of L_0, L_1, L_2 lie side by side: the head adds to all three, the background's is not reported)
+            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth', 'g_rec_region'], self.device,
+                                          extra=['g_rec_bg', 'g_rec_hand', 'g_rec_obj'])
         self._d_terms = ops.LossSlots(['d'], self.device, extra=['d_real', 'd_fake'] + (['d_reg'] if self._lecam is not None else []))
         z = lambda: torch.zeros((), device=self.device)
         self._loss_g_rec, self._loss_g_tsf, self._loss_g_adv = z(), z(), z()
@@ -366,6 +377,9 @@ class Trainer(BaseModel):
                 n['input_G_bg'], n['src_obj_rgb'], n['tsf_obj_rgb'], n['src_hand_cond'], n['tsf_hand_cond'], n['src_obj_cond'],
                 n['tsf_obj_cond'], n.get('armask_src'), n.get('armask_tsf'))
             n['d_real_in'] = ops.cat_channels([n['real_tsf'], n['tsf_cond']])
+            if self._region is not None:       # the label maps of both views, source first: 1 hand, 2 object, 0 neither
+                from ..metrics.regions import labels_from_masks
+                n['region_labels'] = labels_from_masks(n['bg_mask'][..., 0], n['hand_mask'][..., 0])
         return n
 
     def set_prepared_input(self, inp):
@@ -742,7 +756,11 @@ class Trainer(BaseModel):
             self._wait_d()
             d_fake = self._D.forward_nhwc(self._d_fake_in(fake_tsf))
             self._loss_g_adv = self._g_adv_loss(d_fake, into('g_adv'))
-        self._loss_g_rec = ops.l1_loss(fake_src, n['real_src'], o.lambda_rec, into=into('g_rec'))
+        if self._region is None:
+            self._loss_g_rec = ops.l1_loss(fake_src, n['real_src'], o.lambda_rec, into=into('g_rec'))
+            rec = [self._loss_g_rec]
+        else:
+            rec = self._region_losses(fake_src, fake_tsf)
         # the reference uses self._crt_tsf in both branches of `if use_vgg` (:443-446); it only exists with --use_vgg
         tsf = self._crt_tsf.forward_nhwc(fake_tsf, n['real_tsf'], o.lambda_tsf, side=s_vgg, into=into('g_tsf'))
         if fork:
@@ -756,7 +774,28 @@ class Trainer(BaseModel):
         # every term already sits, scaled, in its slot: one launch sums them; the reported values are views of the slots
         self._loss_g_tsf, self._loss_g_mask = T.value('g_tsf'), T.value('g_mask')
         self._loss_g_mask_smooth = T.value('g_mask_smooth')
-        return T.total(self._loss_g_adv, self._loss_g_rec, *(tsf + masks + smooth))
+        return T.total(self._loss_g_adv, *(rec + tsf + masks + smooth))
+
+    def _region_losses(self, fake_src, fake_tsf):
+        """g_rec and the region terms (docs/region_loss.md).  Source view: one fused head in place of ops.l1_loss -- the whole-frame term
+        goes to g_rec's slot as before, the hand's and the object's to g_rec_region.  Target view: the region terms alone.  On the
+        caller's stream; the counts and scales never leave the device."""
+        from ..region_loss import region_l1_loss
+        o, n, g, into = self._opt, self._n, self._region, self._g_terms.term
+        B = fake_src.shape[0]
+        labels, lam = n['region_labels'], (0.0, g['hand'], g['obj'])
+        out = []
+        if g['views'] in ('both', 'src'):
+            out.append(region_l1_loss(fake_src, n['real_src'], labels[:B], lam, o.lambda_rec, g['min_pixels'], into('g_rec_region'),
+                                      into_regions=into('g_rec_bg'), into_all=into('g_rec')))
+            self._loss_g_rec = self._g_terms.value('g_rec')
+        else:
+            self._loss_g_rec = ops.l1_loss(fake_src, n['real_src'], o.lambda_rec, into=into('g_rec'))
+            out.append(self._loss_g_rec)
+        if g['views'] in ('both', 'tsf'):
+            out.append(region_l1_loss(fake_tsf, n['real_tsf'], labels[B:], lam, 0.0, g['min_pixels'], into('g_rec_region'),
+                                      into_regions=into('g_rec_bg')))
+        return out
 
     def _g_adv_loss(self, d_fake, into):
         """g_adv on D(fake): the reference's least-squares term against 0, or the generator's term of gan_mode (never a LeCam term)."""
@@ -847,6 +886,9 @@ class Trainer(BaseModel):
             out['lecam_real'], out['lecam_fake'] = r['real'], r['fake']
             out['d_reg'] = self._d_terms.value('d_reg').item()
             out['lecam_bad'] = r['bad']
+        if self._region is not None:                  # (the objective's region slot; the unweighted L_hand and L_obj over the views)
+            for k in ('g_rec_region', 'g_rec_hand', 'g_rec_obj'):
+                out[k] = self._g_terms.value(k).item()
         return out
 
     def grad_report(self):

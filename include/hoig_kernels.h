@@ -1137,6 +1137,42 @@ int hoig_gan_g_loss(int mode, const float *b, int64_t n_b, double s, float *db, 
                     hoig_stream_t stream);
 int hoig_gan_g_loss_host(int mode, const float *b, int64_t n_b, double s, float *db, float *term);
 
+/* ---- OPT-IN REGION RECONSTRUCTION TERM FOR G (hoig_amd/csrc/region_loss.hip, region_loss.h, region_loss_host.cpp;
+ *      hoig_amd/region_loss.py; docs/region_loss.md).  An L1 term per labelled region, each normalised by the region's own pixel
+ *      count in its image, beside the whole-frame L1; the counts, the validity of every (image, region) row and the gradient scales
+ *      are made and consumed on the device in the same call.  pred, target: fp32 [N][H][W][C]; labels: uint8 [N][H][W], 0 .. R.
+ *      With n_ir the pixels of image i labelled r, row (i, r) valid when n_ir >= min_pixels, V_r the valid images of region r, d =
+ *      pred - target:
+ *        L_r   = (1 / V_r) sum_{i valid} (1 / (C n_ir)) sum_{p in r, c} |d|        (0 when V_r = 0)
+ *        L_all = (1 / (N H W C)) sum |d|
+ *        dpred = sign(d) ((float)(lambda_all / (N H W C)) + (valid_ir ? (float)(lambda_r / (V_r C n_ir)) : 0))   (NULL: not written)
+ *        *term      += (float)(sum_r lambda_r L_r)     -- plus lambda_all L_all when term_all is NULL
+ *        *term_all  += (float)(lambda_all L_all)       (may be NULL)
+ *        terms_r[r] += (float)L_r, r = 0 .. R          (unweighted report slots; may be NULL)
+ *        counts_out[i][r] = n_ir                       (int32 [N][R + 1]; may be NULL)
+ *        *status = 0, or HOIG_REGION_BAD_LABEL with the largest label above R in bits 8 .. 15 (such a pixel is in L_all only)
+ *      sign(0) = 0, and a NaN difference gets the gradient 0 (its sums are NaN).  Every floating-point sum is fp64 in an order fixed
+ *      by (N, H, W, C): no floating-point atomics, no wait between workgroups; the counts are integer atomics.  One memset node and
+ *      three launches on `stream`; never synchronises, allocates nothing.  The *_host twin takes host memory, makes no HIP call and
+ *      gives the device's bits.  HOIG_EINVAL, and nothing launched, for a NULL or misaligned pointer (floats, int32: 4 bytes;
+ *      workspace: 16), N outside 1 .. HOIG_RLOSS_MAX_N, H or W outside 1 .. 4096, C outside 1 .. HOIG_RLOSS_MAX_C, R outside
+ *      0 .. HOIG_RLOSS_MAX_R, a negative or non-finite weight, min_pixels < 1, a short workspace, or a dpred that overlaps pred,
+ *      target or labels. ---- */
+#define HOIG_RLOSS_MAX_R 7         /* the most regions (label values 1 .. 7, as HOIG_REGION_MAX) */
+#define HOIG_RLOSS_MAX_N 4096      /* the most images of a call */
+#define HOIG_RLOSS_MAX_C 64        /* the most channels */
+#define HOIG_RLOSS_THREADS 256     /* threads of a workgroup */
+#define HOIG_RLOSS_TILE 4096       /* floats of one image that a workgroup of the value-and-gradient launch takes */
+#define HOIG_RLOSS_COUNT_TILE 4096 /* labels of one image that a workgroup of the counting launch takes */
+int64_t hoig_region_loss_workspace_bytes(int N, int H, int W, int C, int R);
+int hoig_region_loss(const float *pred, const float *target, const uint8_t *labels, int N, int H, int W, int C, int R,
+                     const double *lambda /*[R + 1], host memory*/, double lambda_all, int min_pixels, float *dpred, float *term,
+                     float *terms_r, float *term_all, int32_t *counts_out, int32_t *status, void *workspace, int64_t workspace_bytes,
+                     hoig_stream_t stream);
+int hoig_region_loss_host(const float *pred, const float *target, const uint8_t *labels, int N, int H, int W, int C, int R,
+                          const double *lambda, double lambda_all, int min_pixels, float *dpred, float *term, float *terms_r,
+                          float *term_all, int32_t *counts_out, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif
