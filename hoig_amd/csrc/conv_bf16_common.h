@@ -1,5 +1,5 @@
-// Shared pieces of the 16-bit-operand convolution kernels (conv_igemm_bf16.hip, conv_halo16.hip): the split helpers, the
-// blocked weight-plane layout and the argument block of the LDS-halo kernels.
+// Shared pieces of the 16-bit-operand convolution kernels (conv_igemm_bf16.hip, conv_halo32.hip, conv_halo16.hip, weight_planes.hip):
+// the split helpers, the blocked weight-plane layout, the kernels' argument blocks and the launchers the dispatcher calls.
 #pragma once
 #include "common.h"
 
@@ -83,35 +83,35 @@ __device__ __forceinline__ void split4t(const float4 v, uint2 &hi, uint2 &lo) {
 // ((n/32) * (K/32) + k/32) * 1024.  The weight tile of one k-step (BN rows x 32 k) is then BN/32 fully used 2-KB runs
 // instead of BN half-used 128-B lines K*2 bytes apart; N and K are multiples of 32 on this path.  Inside a block, row n
 // holds its four 16-B chunks at position chunk ^ ((n >> 2) & 3): the block is byte for byte the XOR-swizzled LDS image
-// the kernels read (lds_swz<32>), so a tile can be copied to LDS linearly -- by global_load_lds, 1 KB per wave-instruction.
+// the kernels read (lds_swz<32> of conv_igemm_bf16.hip), so a tile can be copied to LDS linearly -- by global_load_lds, 1 KB per wave-instruction.
 __host__ __device__ __forceinline__ size_t plane_index(int n, int k, int K) {
     return ((size_t)(n >> 5) * (K >> 5) + (k >> 5)) * 1024 + (n & 31) * 32 + (((((k & 31) >> 3) ^ ((n >> 2) & 3))) << 3) +
            (k & 7);
 }
 
 struct HaloArgs {
-    const float *A;
-    const unsigned short *Wh, *Wl;
-    const float *bias;
-    float *C;
-    int Bn, H, W, Cg;       // input == output spatial size (stride 1, "same" padding), gathered channels
-    int N, K;               // output channels, KS*KS*Cg
-    int pad;                // halo origin = tile origin - pad   (dgrad: KS-1-pad)
-    int flip;               // 1: weight tap index = KS*KS-1 - (r*KS+s)   (data gradient)
-    int act;
-    float slope;
-    int nblk_n, nblk;
-    int tiles_x, tiles_y;
-    int nmajor;                // tile index = channel tile * pixel tiles + pixel tile (3x3 kernel)
-    int f16;                   // forward launch: fp16-split operands, weights pre-scaled by 2^8
-    float oscale;              // accumulator scale of the epilogue (2^-8 or 1)
+    const float *A = nullptr;
+    const unsigned short *Wh = nullptr, *Wl = nullptr;
+    const float *bias = nullptr;
+    float *C = nullptr;
+    int Bn = 0, H = 0, W = 0, Cg = 0;       // input == output spatial size (stride 1, "same" padding), gathered channels
+    int N = 0, K = 0;                       // output channels, KS*KS*Cg
+    int pad = 0;                            // halo origin = tile origin - pad   (dgrad: KS-1-pad)
+    int flip = 0;                           // 1: weight tap index = KS*KS-1 - (r*KS+s)   (data gradient)
+    int act = 0;
+    float slope = 0.f;
+    int nblk_n = 0, nblk = 0;
+    int tiles_x = 0, tiles_y = 0;
+    int nmajor = 0;            // tile index = channel tile * pixel tiles + pixel tile (3x3 kernel)
+    int f16 = 0;               // forward launch: fp16-split operands, weights pre-scaled by 2^8
+    float oscale = 0.f;        // accumulator scale of the epilogue (2^-8 or 1)
     // channel concatenation without the copy (3x3 kernel): the gathered tensor is [A | A2] along channels (A holds the
     // first cg1 of the Cg channels), and / or the output is [C | C2] (C receives the first n1 of the N columns)
-    const float *A2;
-    int cg1;
-    float *C2;
-    int n1;
-    const float *addend;       // same shape as C (single-output launches only): C = conv + addend -- the data gradient that lands in
+    const float *A2 = nullptr;
+    int cg1 = 0;
+    float *C2 = nullptr;
+    int n1 = 0;
+    const float *addend = nullptr;  // same shape as C (single-output launches only): C = conv + addend -- the data gradient that lands in
                                // a tensor with a second consumer adds that consumer's gradient itself (ops.conv2d_fork)
     // grouped launch (3x3 stride-1 kernel of conv_halo16.hip only): Bn counts the images of BOTH problems; images b >= b_split read and
     // write the *_g2 tensors (indexed from their own image 0).  0: one problem.
@@ -121,39 +121,39 @@ struct HaloArgs {
     // to every pixel inside the image (the zero padding stays zero).  nullptr: off.
     const float *in_scale = nullptr, *in_shift = nullptr;
     int in_relu_c0 = 0;
-    int b_split;
-    const float *A_g2;
-    const unsigned short *Wh_g2, *Wl_g2;
-    const float *bias_g2, *addend_g2;
-    float *C_g2;
-    int a_split;               // 1: A is a PRE-SPLIT tensor, per pixel [hi: Cg bf16][lo: Cg bf16] (hoig_split_planes_bf16): the 3x3
+    int b_split = 0;
+    const float *A_g2 = nullptr;
+    const unsigned short *Wh_g2 = nullptr, *Wl_g2 = nullptr;
+    const float *bias_g2 = nullptr, *addend_g2 = nullptr;
+    float *C_g2 = nullptr;
+    int a_split = 0;           // 1: A is a PRE-SPLIT tensor, per pixel [hi: Cg bf16][lo: Cg bf16] (hoig_split_planes_bf16): the 3x3
                                // stride-1 data gradient on conv_halo16.hip copies it to LDS without splitting (no A2 then)
-    double *stats;             // (nullable) [Bn][2][N] fp64 accumulators: += per-image, per-channel sum and sum of squares of the
+    double *stats = nullptr;   // (nullable) [Bn][2][N] fp64 accumulators: += per-image, per-channel sum and sum of squares of the
                                // values written to C -- the statistics of the instance norm that reads C next
 };
 
 // geometry and argument block of the generic implicit-GEMM kernels (igemm_bf16_kernel in conv_igemm_bf16.hip, conv_igemm16.hip)
 struct Geom {
-    int Bn, Hg, Wg, Cg;
-    int Hp, Wp;
-    int R, S, stride, pad;
-    int gatherT, phase_major, tile_skip;
+    int Bn = 0, Hg = 0, Wg = 0, Cg = 0;
+    int Hp = 0, Wp = 0;
+    int R = 0, S = 0, stride = 0, pad = 0;
+    int gatherT = 0, phase_major = 0, tile_skip = 0;
 };
 
 struct Args {
-    const float *A;
-    const unsigned short *Wh;
-    const unsigned short *Wl;
-    const float *bias;
-    float *C;
+    const float *A = nullptr;
+    const unsigned short *Wh = nullptr;
+    const unsigned short *Wl = nullptr;
+    const float *bias = nullptr;
+    float *C = nullptr;
     Geom g;
-    int M, N, K;
-    int act;
-    float slope;
-    int nblk_n, nblk;
-    int ksplit, steps_per_split;   // split-K over blockIdx.y (atomic epilogue into a zeroed output)
-    int f16;                       // forward launch: fp16-split operands, weights pre-scaled by 2^8
-    float oscale;                  // accumulator scale of the epilogue (2^-8 or 1)
+    int M = 0, N = 0, K = 0;
+    int act = 0;
+    float slope = 0.f;
+    int nblk_n = 0, nblk = 0;
+    int ksplit = 0, steps_per_split = 0;   // split-K over blockIdx.y (atomic epilogue into a zeroed output)
+    int f16 = 0;                           // forward launch: fp16-split operands, weights pre-scaled by 2^8
+    float oscale = 0.f;                    // accumulator scale of the epilogue (2^-8 or 1)
 };
 
 __device__ __forceinline__ void decode_m(const Geom &g, int m, int &b, int &hp, int &wp) {
@@ -198,10 +198,10 @@ __device__ __forceinline__ bool tap_alive(const Geom &g, int hp, int wp, int rs)
 
 // wgrad_flat.hip: weight gradient of valid 5x5 stride-1 convolutions on the flattened pixel axis
 struct WFlatArgs {
-    const float *X, *DY;
-    float *DW, *DB;
-    int Ci, Co, Wc, HWc, Q, Ho, Wo, HPOS;
-    int nblk_ci, nblk, n_mtiles, mt_per_split;
+    const float *X = nullptr, *DY = nullptr;
+    float *DW = nullptr, *DB = nullptr;
+    int Ci = 0, Co = 0, Wc = 0, HWc = 0, Q = 0, Ho = 0, Wo = 0, HPOS = 0;
+    int nblk_ci = 0, nblk = 0, n_mtiles = 0, mt_per_split = 0;
 };
 int launch_wgrad_flat5(const float *x, const float *dy, float *dw, float *dbias, int Bn, int Hi, int Wi, int Ci, int Co, int ns,
                        hipStream_t st);
@@ -212,40 +212,40 @@ int launch_igemm_m16(Args a, int ns, int cfg, hipStream_t st);
 
 // conv_flat16.hip: valid KS x KS convolutions (and their data gradients) on a flattened pixel axis
 struct FlatArgs {
-    const float *A;            // source tensor [Bn][Hs][Ws][Cg]
-    const unsigned short *Wh, *Wl;
-    const float *bias;
-    float *C;                  // destination [Bn][Hd][Wd][N]
-    const float *addend;       // (nullable) same shape as C: C = conv + addend
-    int Bn, Hc, Wc;            // canvas: the grid the taps walk (the input grid of the convolution)
-    int Hs, Ws, oy, ox;        // the source grid and its offset on the canvas (zero elsewhere)
-    int Hd, Wd;                // canvas positions (y < Hd, x < Wd) are outputs
-    int KS, Cg, N, K, flip, f16;
-    int act;
-    float slope, oscale;
-    int HWc, Q, HP;            // filled in by the launcher: Hc * Wc, Bn * Hc * Wc, halo positions per tile
-    int nblk, nblk_n, steps_per_split;
+    const float *A = nullptr;              // source tensor [Bn][Hs][Ws][Cg]
+    const unsigned short *Wh = nullptr, *Wl = nullptr;
+    const float *bias = nullptr;
+    float *C = nullptr;                    // destination [Bn][Hd][Wd][N]
+    const float *addend = nullptr;         // (nullable) same shape as C: C = conv + addend
+    int Bn = 0, Hc = 0, Wc = 0;            // canvas: the grid the taps walk (the input grid of the convolution)
+    int Hs = 0, Ws = 0, oy = 0, ox = 0;    // the source grid and its offset on the canvas (zero elsewhere)
+    int Hd = 0, Wd = 0;                    // canvas positions (y < Hd, x < Wd) are outputs
+    int KS = 0, Cg = 0, N = 0, K = 0, flip = 0, f16 = 0;
+    int act = 0;
+    float slope = 0.f, oscale = 0.f;
+    int HWc = 0, Q = 0, HP = 0;            // filled in by the launcher: Hc * Wc, Bn * Hc * Wc, halo positions per tile
+    int nblk = 0, nblk_n = 0, steps_per_split = 0;
 };
 int launch_flat_m16(FlatArgs a, int ns, hipStream_t st);
 // conv_halo5.hip: valid 5x5 convolutions (and their data gradients) over maps too wide for the flattened axis, on 16 x 16 pixel tiles
 int launch_halo5_m16(FlatArgs a, int ns, hipStream_t st);
 
-// argument block of the weight-gradient halo kernels (wgrad_halo_bf16_kernel in conv_igemm_bf16.hip, wgrad_dma.hip)
+// argument block of the weight-gradient halo kernels (wgrad_halo_bf16_kernel in wgrad_igemm_bf16.hip, wgrad_dma.hip)
 struct WHaloArgs {
-    const float *DY, *X, *X2;  // X2 (nullable): the input is [X | X2] along channels, X holding the first ci1
-    int ci1;
-    float *DW, *DB;            // DB (nullable): bias gradient = column sums of dy, taken from the dy tiles as they are staged
-    int Bn, H, W, Co, Ci;     // H, W: output (= dy) size
-    int Hin, Win, pad;         // input (= x) size and padding
-    int tout;                  // 1: the accumulator tile is [DY channel][X channel] but DW is laid out [X channel][tap][DY channel]
+    const float *DY = nullptr, *X = nullptr, *X2 = nullptr;      // X2 (nullable): the input is [X | X2] along channels, X holds the first ci1
+    int ci1 = 0;
+    float *DW = nullptr, *DB = nullptr;    // DB (nullable): bias gradient = column sums of dy, taken from the dy tiles as they are staged
+    int Bn = 0, H = 0, W = 0, Co = 0, Ci = 0;    // H, W: output (= dy) size
+    int Hin = 0, Win = 0, pad = 0;         // input (= x) size and padding
+    int tout = 0;                          // 1: the accumulator tile is [DY channel][X channel] but DW is laid out [X channel][tap][DY channel]
                                // (ConvTranspose2d stride 2: the plain operand is x, the gathered one dy -- roles swapped)
-    int tiles_x, tiles_y, n_mtiles, mt_per_split;
-    int nblk_ci, nblk;
+    int tiles_x = 0, tiles_y = 0, n_mtiles = 0, mt_per_split = 0;
+    int nblk_ci = 0, nblk = 0;
     // grouped launch (wgrad_dma.hip only): Bn counts the images of BOTH problems; a workgroup whose pixel tiles lie in images >= b_split
     // reads DY_g2 / X_g2 (indexed from their own image 0) and adds into DW_g2; a workgroup's tile range never straddles the two
-    int b_split;
-    const float *DY_g2, *X_g2;
-    float *DW_g2;
+    int b_split = 0;
+    const float *DY_g2 = nullptr, *X_g2 = nullptr;
+    float *DW_g2 = nullptr;
 };
 
 // wgrad_dma.hip: the stride-1 3x3 weight gradient from PRE-SPLIT dy (a.DY points at [pixel][2][Co] bf16: hoig_split_planes_bf16 or a
@@ -259,5 +259,14 @@ int launch_wgrad_dma(const WHaloArgs &a, int ns, dim3 grid, hipStream_t st);
 // or 64; `a` carries that tiling's geometry); HOIG_EUNSUPPORTED for shapes it has no tiling for
 int launch_halo3_m16(HaloArgs a, int ns, int bn, hipStream_t st);
 int launch_halo_s2_m16(const HaloArgs &a, int ns, bool scatter, hipStream_t st);
+
+// conv_halo32.hip: the halo kernels on v_mfma_f32_32x32x16 and the choice between them and the 16x16 tiles above.  `a` carries the
+// tensors, sizes and epilogue; the launcher sets the tiling.  launch_halo: stride-1 "same" 1x1 / 5x5 (KS = 1, 5); launch_halo3: stride-1
+// 3x3; launch_halo_s2: stride-2 3x3, a.H x a.W the size of the gathered tensor
+template <int KS>
+int launch_halo(HaloArgs a, int ns, hipStream_t st);
+int launch_halo3(HaloArgs a, int ns, hipStream_t st);
+template <bool SCATTER>
+int launch_halo_s2(HaloArgs a, int ns, hipStream_t st);
 
 }  // namespace hoig_detail

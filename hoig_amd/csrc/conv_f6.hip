@@ -55,7 +55,7 @@ constexpr float W_SCALE = 256.f;
 struct F6Args {
     const float *A, *A2;                      // A2 (nullable): the input is [A | A2] along channels, A holding the first cg1 (% 32)
     int cg1;
-    const unsigned short *Wh;                 // fp16 hi plane of w * 2^8, blocked 32(n) x 32(k) (plane_index of conv_igemm_bf16.hip)
+    const unsigned short *Wh;                 // fp16 hi plane of w * 2^8, blocked 32(n) x 32(k) (plane_index of conv_bf16_common.h)
     const unsigned char *Qh, *Ql;             // fp6 records of hi / lo: [(tap * ncb64 + cb64)][n][REC]
     const float *bias;
     float *C;
@@ -509,9 +509,7 @@ extern "C" int hoig_pack_conv_weight_f6(const float *w, int Co, int RS, int Ci, 
     if (!w || !q_hi || !q_lo || Co <= 0 || RS <= 0) return HOIG_EINVAL;
     if (Ci & 63) return HOIG_EUNSUPPORTED;
     const int64_t n = (int64_t)Co * RS * (Ci >> 5);
-    pack_f6_kernel<<<hoig_stream_grid(n, 256), 256, 0, (hipStream_t)stream>>>(w, Co, RS, Ci, q_hi, q_lo);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<pack_f6_kernel>(hoig_stream_grid(n, 256), 256, 0, (hipStream_t)stream, w, Co, RS, Ci, q_hi, q_lo);
 }
 
 // forward 3x3 stride-1 pad-1 convolution; HOIG_EUNSUPPORTED for every shape outside this kernel's tiling (the caller then uses
@@ -561,16 +559,9 @@ extern "C" int hoig_conv2d_fwd_f6(const hoig_conv_desc *d, const float *x, const
     if (!d || !x || !w_hi || !q_hi || !q_lo || !y) return HOIG_EINVAL;
     return launch_f6(d, x, nullptr, 0, w_hi, q_hi, q_lo, bias, y, (hipStream_t)stream);
 }
-// the same over the channel concatenation [x1 | x2] without materialising it (the decoder's skip convolutions)
-extern "C" int hoig_conv2d_cat_fwd_f6(const hoig_conv_desc *d, const float *x1, int C1, const float *x2, const uint16_t *w_hi,
-                                      const uint8_t *q_hi, const uint8_t *q_lo, const float *bias, float *y,
-                                      hoig_stream_t stream) {
-    if (!d || !x1 || !x2 || !w_hi || !q_hi || !q_lo || !y) return HOIG_EINVAL;
-    return launch_f6(d, x1, x2, C1, w_hi, q_hi, q_lo, bias, y, (hipStream_t)stream);
-}
 
-// hoig_conv2d_fwd_f6 / hoig_conv2d_cat_fwd_f6 with the loader and epilogue options of the three-term path (include/hoig_kernels.h):
-// x2 (nullable) = the second tensor of a channel concatenation; in_scale / in_shift (nullable, together) = the instance norm + ReLU of
+// hoig_conv2d_fwd_f6 with the loader and epilogue options of the three-term path (include/hoig_kernels.h):
+// x2 (nullable) = the second tensor of a channel concatenation [x | x2], never materialised (the decoder's skip convolutions); in_scale / in_shift (nullable, together) = the instance norm + ReLU of
 // the gathered tensor applied in the loader; stats (nullable) = the per-image channel sums of y for the norm that follows
 extern "C" int hoig_conv2d_fwd_f6_ex(const hoig_conv_desc *d, const float *x, int C1, const float *x2, const uint16_t *w_hi,
                                      const uint8_t *q_hi, const uint8_t *q_lo, const float *bias, const float *in_scale,
@@ -582,9 +573,7 @@ extern "C" int hoig_conv2d_fwd_f6_ex(const hoig_conv_desc *d, const float *x, in
 extern "C" int hoig_pack_conv_weights_f6_all(const float *flat, const int64_t *rows, int nrows, int64_t ntasks, uint8_t *q_hi,
                                              uint8_t *q_lo, hoig_stream_t stream) {
     if (!flat || !rows || nrows <= 0 || ntasks <= 0 || !q_hi || !q_lo) return HOIG_EINVAL;
-    pack_f6_all_kernel<<<hoig_stream_grid(ntasks, 256), 256, 0, (hipStream_t)stream>>>(flat, rows, nrows, ntasks, q_hi, q_lo);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<pack_f6_all_kernel>(hoig_stream_grid(ntasks, 256), 256, 0, (hipStream_t)stream, flat, rows, nrows, ntasks, q_hi, q_lo);
 }
 
 extern "C" int hoig_set_f6_min_tiles(int n) {

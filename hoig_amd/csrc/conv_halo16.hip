@@ -1,5 +1,5 @@
 // 3x3 stride-1 "same" convolution (forward and data gradient) on v_mfma_f32_16x16x32_{f16,bf16}: the same workgroup tile and
-// step structure as conv_halo3_bf16_kernel MODE 2 (conv_igemm_bf16.hip: 8 rows x 32 pixels x BN channels, 8 waves, the input
+// step structure as conv_halo3_bf16_kernel MODE 2 (conv_halo32.hip: 8 rows x 32 pixels x BN channels, 8 waves, the input
 // halo of a 32-channel block staged once and split to 16-bit hi / lo planes, one TAP ROW of weight tiles per step,
 // double-buffered), on the 16x16 MFMA shape, which holds a higher clock than 32x32x16 on random data (MI355X_MICROARCH.md,
 // 'DVFS give-back' item 7; cdna_hip_programming.md rule 28).
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_halo3_m16_kernel(const Halo
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Stride-2 3x3 layers (Conv2d s2 p1 and ConvTranspose2d s2 p1 op1, forward and data gradient) on the 16x16 MFMA: the parity-phase
-// decomposition, step table and tile of conv_halo_s2_bf16_kernel (conv_igemm_bf16.hip: 4 x 32 coarse pixels x BN channels, four
+// decomposition, step table and tile of conv_halo_s2_bf16_kernel (conv_halo32.hip: 4 x 32 coarse pixels x BN channels, four
 // waves, steps of <= 2 taps over a (4+1) x 33 halo image, two workgroups per CU), with the LDS images and the swapped operand
 // roles of conv_halo3_m16_kernel above (a lane ends up with four consecutive channels of one pixel: 16-B stores, also strided
 // over the fine grid in scatter mode).
@@ -712,7 +712,7 @@ int launch_s2(const HaloArgs &a, int ns, hipStream_t st) {
 
 }  // namespace
 
-// the stride-2 3x3 layers: `a` arrives with the geometry launch_halo_s2 (conv_igemm_bf16.hip) computes
+// the stride-2 3x3 layers: `a` arrives with the geometry launch_halo_s2 (conv_halo32.hip) computes
 int launch_halo_s2_m16(const HaloArgs &a, int ns, bool scatter, hipStream_t st) {
     if (a.N % 64 || a.Cg % 32) return HOIG_EUNSUPPORTED;
     return scatter ? launch_s2<true>(a, ns, st) : launch_s2<false>(a, ns, st);

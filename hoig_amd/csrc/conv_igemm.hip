@@ -26,33 +26,33 @@
 namespace {
 
 struct Geom {
-    int Bn, Hg, Wg, Cg;  // gathered tensor [Bn][Hg][Wg][Cg]
-    int Hp, Wp;          // pixel grid enumerated by m (per image)
-    int R, S, stride, pad;
-    int gatherT;      // 0: gather_F, 1: gather_T
-    int phase_major;  // m enumerates (ph,pw,b,hp/2,wp/2)
-    int tile_skip;    // tiles have a uniform phase and a k-block lies inside one tap -> skip dead taps
+    int Bn = 0, Hg = 0, Wg = 0, Cg = 0;  // gathered tensor [Bn][Hg][Wg][Cg]
+    int Hp = 0, Wp = 0;                  // pixel grid enumerated by m (per image)
+    int R = 0, S = 0, stride = 0, pad = 0;
+    int gatherT = 0;      // 0: gather_F, 1: gather_T
+    int phase_major = 0;  // m enumerates (ph,pw,b,hp/2,wp/2)
+    int tile_skip = 0;    // tiles have a uniform phase and a k-block lies inside one tap -> skip dead taps
 };
 
 struct IgemmArgs {
-    const float *A;
-    const float *W;
-    const float *bias;
-    float *C;
+    const float *A = nullptr;
+    const float *W = nullptr;
+    const float *bias = nullptr;
+    float *C = nullptr;
     Geom g;
-    int M, N, K;
-    int act;
-    float slope;
-    int nblk_n, nblk;
+    int M = 0, N = 0, K = 0;
+    int act = 0;
+    float slope = 0.f;
+    int nblk_n = 0, nblk = 0;
 };
 
 struct WgradArgs {
-    const float *X;   // gathered tensor
-    const float *DY;  // [M][Co] over the pixel grid
-    float *DW;        // [Co][K]
+    const float *X = nullptr;   // gathered tensor
+    const float *DY = nullptr;  // [M][Co] over the pixel grid
+    float *DW = nullptr;        // [Co][K]
     Geom g;
-    int M, Co, K;
-    int nblk_n, nblk_mn, m_per_split;
+    int M = 0, Co = 0, K = 0;
+    int nblk_n = 0, nblk_mn = 0, m_per_split = 0;
 };
 
 __device__ __forceinline__ void decode_m(const Geom &g, int m, int &b, int &hp, int &wp) {
@@ -670,10 +670,8 @@ static int launch_wgrad(WgradArgs a, hipStream_t st) {
     else if (BM == 64) HOIG_ROUTE_W(wgrad_f32_64x128);
     else if (BN == 64) HOIG_ROUTE_W(wgrad_f32_128x64);
     else HOIG_ROUTE_W(wgrad_f32_128x128);
-    if (a.g.Cg % 4 == 0) wgrad_f32_kernel<BM, BN, WM, WN, 4><<<grid, block, 0, st>>>(a);
-    else wgrad_f32_kernel<BM, BN, WM, WN, 1><<<grid, block, 0, st>>>(a);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (a.g.Cg % 4 == 0) return hoig_launch<wgrad_f32_kernel<BM, BN, WM, WN, 4>>(grid, block, 0, st, a);
+    return hoig_launch<wgrad_f32_kernel<BM, BN, WM, WN, 1>>(grid, block, 0, st, a);
 }
 
 // bytes of per-stream scratch (hoig_stream_scratch_set) hoig_conv2d_bwd_weight wants for this layer: 0 for all but the thin-channel ones

@@ -21,7 +21,7 @@
     W(wgrad_f32_32x64) W(wgrad_f32_32x128) W(wgrad_f32_64x128) W(wgrad_f32_128x64) W(wgrad_f32_128x128)                            \
     /* conv_igemm.hip: launch_igemm<BM, BN> in fp32 */                                                                             \
     FD(igemm_f32_128x32) FD(igemm_f32_128x64) FD(igemm_f32_64x64) FD(igemm_f32_128x128) FD(igemm_f32_64x128)                       \
-    /* conv_igemm_bf16.hip: launch_halo<1>, launch_halo<5> (64-channel tiles, 128 on 8 waves, 128 on 4 waves) */                   \
+    /* conv_halo32.hip: launch_halo<1>, launch_halo<5> (64-channel tiles, 128 on 8 waves, 128 on 4 waves) */                       \
     FD(halo1_64) FD(halo1_128w) FD(halo1_128) FD(same5_64) FD(same5_128w) FD(same5_128)                                            \
     /* launch_halo3_one */                                                                                                         \
     FD(halo3_64) FD(halo3_128w) FD(halo3_128)                                                                                      \
@@ -31,7 +31,7 @@
     F(halo3_m16_64_pair) F(halo3_m16_128_pair) F(halo3_m16_64_normin) F(halo3_m16_128_normin)                                      \
     /* conv_flat16.hip, conv_halo5.hip; _ksplit: split over K, added with atomics */                                               \
     FD(flat_m16_k3) FD(flat_m16_k5) FD(halo5_m16) FD(halo5_m16_ksplit)                                                             \
-    /* stride-2 3x3: g gather, s scatter; the 32x32 kernel, conv_halo16.hip (m16), conv_s2_16.hip (m16p4: 4-row, m16p8: 8-row tiles) */ \
+    /* stride-2 3x3: g gather, s scatter; conv_halo32.hip, conv_halo16.hip (m16), conv_s2_16.hip (m16p4: 4-row, m16p8: 8-row tiles) */ \
     FD(s2g_64) FD(s2g_128) FD(s2s_64) FD(s2s_128)                                                                                  \
     FD(s2g_m16_64) FD(s2g_m16_128) FD(s2s_m16_64) FD(s2s_m16_128)                                                                  \
     FD(s2g_m16p4_64) FD(s2g_m16p4_128) FD(s2s_m16p4_64) FD(s2s_m16p4_128) FD(s2g_m16p8_128) FD(s2s_m16p8_128)                      \

@@ -366,7 +366,7 @@ int launch_s2p(const HaloArgs &a, int ns, hipStream_t st) {
 
 }  // namespace
 
-// `a` arrives with the 4-row geometry launch_halo_s2 (conv_igemm_bf16.hip) computes; rows8: re-tile to 8 x 32 (the caller has checked
+// `a` arrives with the 4-row geometry launch_halo_s2 (conv_halo32.hip) computes; rows8: re-tile to 8 x 32 (the caller has checked
 // that the coarse height is a multiple of 8 and N of 128)
 int launch_halo_s2_m16p(const HaloArgs &a_, int ns, bool scatter, bool rows8, hipStream_t st) {
     if (!rows8) return scatter ? launch_s2p<true, 2>(a_, ns, st) : launch_s2p<false, 2>(a_, ns, st);

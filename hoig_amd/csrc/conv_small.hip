@@ -347,19 +347,17 @@ int hoig_conv_small_fwd_acts(const hoig_conv_desc *d, const float *x, const floa
     if (d->transposed || d->stride != 1 || d->Co > 5 || (d->Ci % CC) || d->R != KS || d->S != KS) return HOIG_EUNSUPPORTED;
     if (d->Ho != d->Hi || d->Wo != d->Wi || 2 * d->pad != d->R - 1 || d->R != d->S) return HOIG_EUNSUPPORTED;
     const int tiles = d->B * (int)hoig_cdiv(d->Hi, F4_TH) * (int)hoig_cdiv(d->Wi, F4_TW);
-#define HOIG_SMALL_FWD(N)                                                                                          \
-    conv_small_fwd4_kernel<N><<<tiles, 256, 0, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->pad, acts, d->slope, d->Co)
+#define HOIG_SMALL_FWD(N) \
+    hoig_launch<conv_small_fwd4_kernel<N>>(tiles, 256, 0, st, x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->pad, acts, d->slope, d->Co)
     HOIG_ROUTE_F(small);
     switch (d->Co) {
-        case 1: HOIG_SMALL_FWD(1); break;
-        case 2: HOIG_SMALL_FWD(2); break;
-        case 3: HOIG_SMALL_FWD(3); break;
-        case 4: HOIG_SMALL_FWD(4); break;
-        default: HOIG_SMALL_FWD(5); break;
+        case 1: return HOIG_SMALL_FWD(1);
+        case 2: return HOIG_SMALL_FWD(2);
+        case 3: return HOIG_SMALL_FWD(3);
+        case 4: return HOIG_SMALL_FWD(4);
+        default: return HOIG_SMALL_FWD(5);
     }
 #undef HOIG_SMALL_FWD
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
 }
 int hoig_conv_small_fwd(const hoig_conv_desc *d, const float *x, const float *w, const float *bias, float *y,
                         hipStream_t st) {
@@ -381,18 +379,19 @@ int hoig_conv_small_ci_fwd(const hoig_conv_desc *d, const float *x, const float 
         const bool last = off + 4 >= d->Ci;
         const float *bb = last ? bias : nullptr;
         const int act = last ? d->act : HOIG_ACT_NONE;
-#define HOIG_SMALL_CF(N) \
-    conv_small_dgrad4_kernel<N, true><<<grid, 256, 0, st>>>(x, w, y, d->B, d->Hi, d->Wi, d->Co, d->pad, d->Ci, off,       \
-                                                            off > 0 ? 1 : 0, bb, act, d->slope)
+#define HOIG_SMALL_CF(N)                                                                                                      \
+    hoig_launch<conv_small_dgrad4_kernel<N, true>>(grid, 256, 0, st, x, w, y, d->B, d->Hi, d->Wi, d->Co, d->pad, d->Ci, off, \
+                                                   off > 0 ? 1 : 0, bb, act, d->slope)
         HOIG_ROUTE_F(small_ci);
+        int rc;
         switch (n) {
-            case 1: HOIG_SMALL_CF(1); break;
-            case 2: HOIG_SMALL_CF(2); break;
-            case 3: HOIG_SMALL_CF(3); break;
-            default: HOIG_SMALL_CF(4); break;
+            case 1: rc = HOIG_SMALL_CF(1); break;
+            case 2: rc = HOIG_SMALL_CF(2); break;
+            case 3: rc = HOIG_SMALL_CF(3); break;
+            default: rc = HOIG_SMALL_CF(4); break;
         }
 #undef HOIG_SMALL_CF
-        HOIG_LAUNCH_CHECK();
+        if (rc != HOIG_OK) return rc;
     }
     return HOIG_OK;
 }
@@ -401,19 +400,17 @@ int hoig_conv_small_dgrad(const hoig_conv_desc *d, const float *dy, const float 
     if (d->transposed || d->stride != 1 || d->Co > 4 || (d->Ci % 16) || d->R != KS || d->S != KS) return HOIG_EUNSUPPORTED;
     if (d->Ho != d->Hi || d->Wo != d->Wi || 2 * d->pad != d->R - 1) return HOIG_EUNSUPPORTED;
     dim3 grid(d->B * (unsigned)hoig_cdiv(d->Hi, F4_TH) * (unsigned)hoig_cdiv(d->Wi, F4_TW), d->Ci / 16);
-#define HOIG_SMALL_DG(N) \
-    conv_small_dgrad4_kernel<N, false><<<grid, 256, 0, st>>>(dy, w, dx, d->B, d->Hi, d->Wi, d->Ci, d->pad, d->Co, 0, 0, \
-                                                             nullptr, 0, 0.f)
+#define HOIG_SMALL_DG(N)                                                                                                        \
+    hoig_launch<conv_small_dgrad4_kernel<N, false>>(grid, 256, 0, st, dy, w, dx, d->B, d->Hi, d->Wi, d->Ci, d->pad, d->Co, 0, 0, \
+                                                    nullptr, 0, 0.f)
     HOIG_ROUTE_D(small);
     switch (d->Co) {
-        case 1: HOIG_SMALL_DG(1); break;
-        case 2: HOIG_SMALL_DG(2); break;
-        case 3: HOIG_SMALL_DG(3); break;
-        default: HOIG_SMALL_DG(4); break;
+        case 1: return HOIG_SMALL_DG(1);
+        case 2: return HOIG_SMALL_DG(2);
+        case 3: return HOIG_SMALL_DG(3);
+        default: return HOIG_SMALL_DG(4);
     }
 #undef HOIG_SMALL_DG
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
 }
 
 int hoig_conv_small_wgrad(const hoig_conv_desc *d, const float *x, const float *dy, float *dw, hipStream_t st) {
@@ -425,17 +422,15 @@ int hoig_conv_small_wgrad(const hoig_conv_desc *d, const float *x, const float *
     while (tpb > 1 && hoig_cdiv(tiles, tpb) * (d->Ci / CC) < 512) tpb >>= 1;
     dim3 grid((unsigned)hoig_cdiv(tiles, tpb), d->Ci / CC);
 #define HOIG_SMALL_WG(N) \
-    conv_small_wgrad_kernel<N><<<grid, 256, 0, st>>>(x, dy, dw, d->B, d->Hi, d->Wi, d->Ci, d->R, d->S, d->pad, d->Co, tpb)
+    hoig_launch<conv_small_wgrad_kernel<N>>(grid, 256, 0, st, x, dy, dw, d->B, d->Hi, d->Wi, d->Ci, d->R, d->S, d->pad, d->Co, tpb)
     HOIG_ROUTE_W(wgrad_small);
     switch (d->Co) {
-        case 1: HOIG_SMALL_WG(1); break;
-        case 2: HOIG_SMALL_WG(2); break;
-        case 3: HOIG_SMALL_WG(3); break;
-        default: HOIG_SMALL_WG(4); break;
+        case 1: return HOIG_SMALL_WG(1);
+        case 2: return HOIG_SMALL_WG(2);
+        case 3: return HOIG_SMALL_WG(3);
+        default: return HOIG_SMALL_WG(4);
     }
 #undef HOIG_SMALL_WG
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
 }
 
 
@@ -487,17 +482,15 @@ int hoig_conv_dot_fwd(const hoig_conv_desc *d, const float *x, const float *w, c
     if (d->transposed || d->Co > 4 || (d->Ci & 3) || d->R * d->S * d->Ci < 1024) return HOIG_EUNSUPPORTED;
     const int64_t outs = (int64_t)d->B * d->Ho * d->Wo;
     const unsigned grid = (unsigned)hoig_cdiv(outs, 4);
-#define HOIG_DOT_FWD(N)                                                                                                    \
-    conv_dot_fwd_kernel<N><<<grid, 256, 0, st>>>(x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->Ho, d->Wo, d->R, d->S, d->stride, \
-                                                 d->pad, d->act, d->slope)
+#define HOIG_DOT_FWD(N)                                                                                                          \
+    hoig_launch<conv_dot_fwd_kernel<N>>(grid, 256, 0, st, x, w, bias, y, d->B, d->Hi, d->Wi, d->Ci, d->Ho, d->Wo, d->R, d->S, d->stride, \
+                                        d->pad, d->act, d->slope)
     HOIG_ROUTE_F(dot);
     switch (d->Co) {
-        case 1: HOIG_DOT_FWD(1); break;
-        case 2: HOIG_DOT_FWD(2); break;
-        case 3: HOIG_DOT_FWD(3); break;
-        default: HOIG_DOT_FWD(4); break;
+        case 1: return HOIG_DOT_FWD(1);
+        case 2: return HOIG_DOT_FWD(2);
+        case 3: return HOIG_DOT_FWD(3);
+        default: return HOIG_DOT_FWD(4);
     }
 #undef HOIG_DOT_FWD
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
 }

@@ -764,9 +764,7 @@ int hoig_conv_thin_wgrad(const hoig_conv_desc *d, const float *x, const float *d
     else if (nfr <= 8) rc = launch_wgrad_t<2, 4>(a, nt, nd, grid, smem, st);
     else rc = launch_wgrad_t<4, 4>(a, nt, nd, grid, smem, st);
     if (rc != HOIG_OK || !a.Ws) return rc;
-    thin_reduce_kernel<<<dim3((unsigned)hoig_cdiv(64 * a.N, NTHR), groups, (unsigned)hoig_cdiv(nwg, 32)), NTHR, 0, st>>>(a, nwg);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<thin_reduce_kernel>(dim3((unsigned)hoig_cdiv(64 * a.N, NTHR), groups, (unsigned)hoig_cdiv(nwg, 32)), NTHR, 0, st, a, nwg);
 }
 
 // forward of a thin-OUTPUT convolution (Co <= 16, Ci % 64 == 0) with per-channel activation codes (4 bits per output channel;

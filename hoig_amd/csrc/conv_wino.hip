@@ -376,9 +376,7 @@ extern "C" int hoig_pack_conv_weight_wino(const float *w, int Co, int Ci, uint16
     if (!w || !u_hi || !u_lo || Co <= 0 || Ci <= 0) return HOIG_EINVAL;
     if ((Co & 15) || (Ci & 31)) return HOIG_EUNSUPPORTED;
     const int frags = (Co >> 4) * (Ci >> 5);
-    pack_wino_kernel<<<(frags + 3) / 4, 256, 0, (hipStream_t)stream>>>(w, Co, Ci, u_hi, u_lo);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<pack_wino_kernel>((frags + 3) / 4, 256, 0, (hipStream_t)stream, w, Co, Ci, u_hi, u_lo);
 }
 
 extern "C" int hoig_conv2d_fwd_wino(const hoig_conv_desc *d, const float *x, const uint16_t *u_hi, const uint16_t *u_lo, const float *bias,

@@ -1,6 +1,6 @@
 // Weight gradient of the stride-1 "same" 3x3 convolutions from PRE-SPLIT dy, staged by LDS-DMA (round 5).
 //
-// wgrad_halo_bf16_kernel (conv_igemm_bf16.hip) pulls fp32 dy through registers: every workgroup loads its 64-KB dy tile, splits
+// wgrad_halo_bf16_kernel (wgrad_igemm_bf16.hip) pulls fp32 dy through registers: every workgroup loads its 64-KB dy tile, splits
 // it to bf16 hi/lo on the VALU and stores it to LDS -- a tile that fifteen other workgroups (the other ci blocks) load and split
 // as well; its waves spend a third of a tile's cycles issuing those loads, 11 % splitting and storing, and the MFMA pipes are
 // busy 40 % (profiles/r03_pmc_dominant_wgrad.json).  Here dy ARRIVES split: its producer (the backward of the norm that follows
@@ -306,16 +306,12 @@ extern "C" int hoig_split_planes_bf16(const float *x, uint16_t *out, int64_t npi
     if (!x || !out || npix < 0 || C <= 0 || (C & 3)) return HOIG_EINVAL;
     if (npix == 0) return HOIG_OK;
     const int64_t n4 = npix * (C / 4);
-    hoig_detail::split_planes_kernel<<<hoig_stream_grid(n4, 256), 256, 0, (hipStream_t)stream>>>(x, out, n4, C / 4);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<hoig_detail::split_planes_kernel>(hoig_stream_grid(n4, 256), 256, 0, (hipStream_t)stream, x, out, n4, C / 4);
 }
 
 extern "C" int hoig_unsplit_planes_bf16(const uint16_t *in, float *out, int64_t npix, int C, hoig_stream_t stream) {
     if (!in || !out || npix < 0 || C <= 0 || (C & 3)) return HOIG_EINVAL;
     if (npix == 0) return HOIG_OK;
     const int64_t n4 = npix * (C / 4);
-    hoig_detail::unsplit_planes_kernel<<<hoig_stream_grid(n4, 256), 256, 0, (hipStream_t)stream>>>(in, out, n4, C / 4);
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    return hoig_launch<hoig_detail::unsplit_planes_kernel>(hoig_stream_grid(n4, 256), 256, 0, (hipStream_t)stream, in, out, n4, C / 4);
 }

@@ -1,6 +1,6 @@
 // Weight gradient of the attention's VALID 5x5 convolutions (models/networks/extract_attn.py:18) on a FLATTENED pixel axis.
 //
-// dW[co][(r,s)][ci] = sum over output positions of dy[pos][co] * x[pos + (r,s)][ci].  wgrad_halo_bf16_kernel (conv_igemm_bf16.hip)
+// dW[co][(r,s)][ci] = sum over output positions of dy[pos][co] * x[pos + (r,s)][ci].  wgrad_halo_bf16_kernel (wgrad_igemm_bf16.hip)
 // does this on 2 x 32-pixel tiles, which needs an output width that is a multiple of 32: the source-side convolution's 36-wide
 // output fell to the generic kernel (160 TFLOP/s: it re-gathers x for each of the 25 taps), and a 64-pixel tile pays a 6 x 36
 // halo for 2 x 32 outputs.  Here the batch is ONE sequence of canvas positions q = (b, y, x) over the INPUT grid (pitch Wc = Wi):

@@ -262,9 +262,7 @@ int launch_wgrad_bf16(WArgs a, int ns, hipStream_t st) {
     dim3 grid(a.nblk_mn, splits);
     if (BM == 64) HOIG_ROUTE_W(wgrad_bf16_64);
     else HOIG_ROUTE_W(wgrad_bf16_128);
-    HOIG_NS_SWITCH(ns, wgrad_bf16_kernel<BM, NSX><<<grid, 256, 0, st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_bf16_kernel<BM, NSX>>(grid, 256, 0, st, a));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -588,13 +586,11 @@ int launch_wgrad_halo(const hoig_conv_desc *d, const float *x, const float *dy, 
         if (ns == 3) return hoig_launch<wgrad_halo_bf16_kernel<3, 3, 2, false, 4>, LDS4>(grid, 768, LDS4, st, a);
         return hoig_launch<wgrad_halo_bf16_kernel<1, 3, 2, false, 4>, LDS4>(grid, 768, LDS4, st, a);
     }
-    if (s2 && cm == 2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 2, true><<<grid, 768, 0, st>>>(a));
-    else if (s2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 1, true><<<grid, 384, 0, st>>>(a));
-    else if (d->R == 5) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 5, 1><<<grid, 640, 0, st>>>(a));
-    else if (cm == 2) HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 2><<<grid, 768, 0, st>>>(a));
-    else HOIG_NS_SWITCH(ns, wgrad_halo_bf16_kernel<NSX, 3, 1><<<grid, 384, 0, st>>>(a));
-    HOIG_LAUNCH_CHECK();
-    return HOIG_OK;
+    if (s2 && cm == 2) HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_halo_bf16_kernel<NSX, 3, 2, true>>(grid, 768, 0, st, a));
+    if (s2) HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_halo_bf16_kernel<NSX, 3, 1, true>>(grid, 384, 0, st, a));
+    if (d->R == 5) HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_halo_bf16_kernel<NSX, 5, 1>>(grid, 640, 0, st, a));
+    if (cm == 2) HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_halo_bf16_kernel<NSX, 3, 2>>(grid, 768, 0, st, a));
+    HOIG_NS_SWITCH(ns, return hoig_launch<wgrad_halo_bf16_kernel<NSX, 3, 1>>(grid, 384, 0, st, a));
 }
 
 }  // namespace

@@ -1104,6 +1104,16 @@ def _x3(d):
     return c
 
 
+def packed_planes(ci, co):
+    """Which packed 16-bit planes a convolution weight with ci input and co output channels has: bit 1 = the forward planes, bit 2 =
+    the data-gradient planes.  A plane is whole 32 x 32 blocks, and the packed-plane kernels want more than 32 output columns (co
+    in the forward, ci in the data gradient).  The one statement of that rule on this side of the library: the launch ladders
+    below and nn.ParamTree's plane table read it."""
+    if ci % 32 or co % 32:
+        return 0
+    return (1 if co > 32 else 0) | (2 if ci > 32 else 0)
+
+
 def _conv_fwd_raw(d, x, w, b, y, transposed=False, norm_next=False):
     """y = conv(x, w) (+bias, activation) on the kernel the precision mode selects.  norm_next: y goes straight into an instance
     norm -- where the layer's kernel can, it also leaves the per-image channel sums of y in the stream's norm workspace
@@ -1116,7 +1126,8 @@ def _conv_fwd_raw(d, x, w, b, y, transposed=False, norm_next=False):
 def _conv_fwd_ladder(d, x, w, b, y, transposed, norm_next):
     """_conv_fwd_raw's launch: the first kernel that takes the layer.  -> True if it left the channel sums of y in the workspace."""
     ws = None
-    if norm_next and d.precision != L.PREC_F32 and d.Ci % 32 == 0 and d.Co % 32 == 0 and d.Co > 32:
+    packed = d.precision != L.PREC_F32 and packed_planes(d.Ci, d.Co) & 1
+    if norm_next and packed:
         ws = _conv_stats_workspace(y)
     elif norm_next and d.precision != L.PREC_F32 and not transposed and d.Ci <= 12 and d.Co % 64 == 0 and d.stride == 1:
         ws0 = _conv_stats_workspace(y)              # the 7x7 stems (thin input): hoig_conv2d_fwd_stats
@@ -1142,7 +1153,7 @@ def _conv_fwd_ladder(d, x, w, b, y, transposed, norm_next):
         hi, lo = _packed_planes(w, transposed, False)
         if L.attempt('hoig_conv2d_fwd_packed_stats', ctypes.byref(d), _p(x), _p(hi), _p(lo), _p(b), _p(y), _p(ws), _st()):
             return True
-    if d.precision != L.PREC_F32 and d.Ci % 32 == 0 and d.Co % 32 == 0 and d.Co > 32:
+    if packed:
         hi, lo = _packed_planes(w, transposed, False)
         if L.attempt('hoig_conv2d_fwd_packed', ctypes.byref(d), _p(x), _p(hi), _p(lo), _p(b), _p(y), _st()):
             return False
@@ -1152,7 +1163,7 @@ def _conv_fwd_ladder(d, x, w, b, y, transposed, norm_next):
 
 def _conv_dgrad_raw(d, g, w, dx, transposed=False, addend=None):
     """dx = data gradient (+ addend: in the kernel's epilogue where it has one, by a separate add otherwise)."""
-    packed = d.precision != L.PREC_F32 and d.Co % 32 == 0 and d.Ci % 32 == 0 and d.Ci > 32
+    packed = d.precision != L.PREC_F32 and packed_planes(d.Ci, d.Co) & 2
     if packed:
         hi, lo = _packed_planes(w, transposed, True)
         if addend is not None and L.attempt('hoig_conv2d_bwd_data_packed_add', ctypes.byref(d), _p(g), _p(hi), _p(lo), _p(addend), _p(dx), _st()):

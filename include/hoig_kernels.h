@@ -198,18 +198,14 @@ int hoig_conv2d_bwd_data_packed_add(const hoig_conv_desc *d, const float *dy, co
  * the hi / lo fp16 halves of 256*w, hoig_f6_plane_bytes(Co, 9, Ci) bytes each, made by hoig_pack_conv_weight_f6 once per
  * optimiser step: [(tap * Ci/64 + ci/64)][co] records of 56 B = 2 x 24 B of e2m3 elements (32 channels each, element j in bits
  * [6j, 6j+6)) + the two E8M0 scale bytes.  w_hi: the forward hi plane of hoig_pack_conv_weight_bf16.  HOIG_EUNSUPPORTED unless
- * Ci % 64 == 0, Co % 64 == 0, H % 8 == 0, W % 32 == 0 and the launch has enough 8x32-pixel tiles to fill the chip.
- * hoig_conv2d_cat_fwd_f6: the same over [x1 | x2] along channels (C1 % 32 == 0) without the concatenated tensor. */
+ * Ci % 64 == 0, Co % 64 == 0, H % 8 == 0, W % 32 == 0 and the launch has enough 8x32-pixel tiles to fill the chip. */
 int64_t hoig_f6_plane_bytes(int Co, int RS, int Ci);
 int hoig_pack_conv_weight_f6(const float *w, int Co, int RS, int Ci, uint8_t *q_hi, uint8_t *q_lo, hoig_stream_t stream);
 int hoig_conv2d_fwd_f6(const hoig_conv_desc *d, const float *x, const uint16_t *w_hi, const uint8_t *q_hi, const uint8_t *q_lo,
                        const float *bias /*nullable*/, float *y, hoig_stream_t stream);
-int hoig_conv2d_cat_fwd_f6(const hoig_conv_desc *d, const float *x1, int C1, const float *x2, const uint16_t *w_hi,
-                           const uint8_t *q_hi, const uint8_t *q_lo, const float *bias /*nullable*/, float *y,
-                           hoig_stream_t stream);
 /* The same kernel with the loader and epilogue options of the three-term path (round 6: eval.py's forward runs on this arithmetic
  * by default, and the inference chain conv - IN - ReLU - conv, generator.py:16-22 / :298-309, keeps its two fusions):
- *   x2 (nullable, C1 % 32 == 0) -- the second tensor of a channel concatenation, as hoig_conv2d_cat_fwd_f6;
+ *   x2 (nullable, C1 % 32 == 0) -- the gathered tensor is [x | x2] along channels, x holding C1 of them, without the concatenated tensor;
  *   in_scale / in_shift (nullable, together; B x Ci floats from hoig_inorm_fold) and in_relu_c0 (% 32 == 0) -- the gathered tensor is
  *     RAW: x * in_scale + in_shift per (image, gathered channel) and ReLU on channels >= in_relu_c0 are applied when the halo is
  *     converted, as hoig_conv2d_fwd_packed_normin does (Ci <= 1024: the image's two rows live in LDS);

@@ -1,5 +1,5 @@
 """What the Adam kernels must compute (adam_kernel, adam_dev_kernel, adam_tick_kernel in hoig_amd/csrc/pointwise.hip, adam_pack_kernel
-in hoig_amd/csrc/conv_igemm_bf16.hip; docs/optimizer_parity.md), without a GPU and without the project's code:
+in hoig_amd/csrc/weight_planes.hip; docs/optimizer_parity.md), without a GPU and without the project's code:
 
   adam64       the update in float64 with exact (double) scalars: the truth.
   adam32_twin  the same in numpy float32, one rounding per operation in the order of the kernel's comment, no FMA, with the six scalars

@@ -1,5 +1,5 @@
 """What a 16-bit operand plane of a convolution weight must contain (pack_weight_kernel, pack_all_kernel and the plane-writing half of
-adam_pack_kernel in hoig_amd/csrc/conv_igemm_bf16.hip; docs/optimizer_parity.md), in numpy, written from the layout's description and
+adam_pack_kernel in hoig_amd/csrc/weight_planes.hip; docs/optimizer_parity.md), in numpy, written from the layout's description and
 importing none of the project's code.
 
 A weight is stored [Co][RS][Ci], fp32.  A plane has N rows of K reduction indices:

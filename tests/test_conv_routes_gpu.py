@@ -154,7 +154,7 @@ ROWS = [
     row('act_bwd_colsum_halo', C(2, 32, 64, 6, 64, 3, 1, 1, bias=Bs, act='sigmoid'), 'wgrad_halo_cm1', F32_128x32),
 ]
 
-# ---- the forward through the launchers it shares with the data gradient (run() in conv_igemm_bf16.hip: the same conditions with
+# ---- the forward through the launchers it shares with the data gradient (run() in conv_igemm_bf16.hip, launchers in conv_halo32.hip: the same conditions with
 # N = Co, and always three fp16 terms): the rows above with Ci and Co swapped.  Full rows, so their backward is checked as well.
 _FWD = [
     ('halo1_64', C(5, 32, 64, 32, 128, 1, 1, 0), 'fwd_halo1_64', None),
