@@ -15,7 +15,7 @@ HIP_FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -I../../include -I. -Wno-u
 HOST_FLAGS="-x c++ -O3 -std=c++17 -fPIC"
 # The per-file exceptions.  -ffp-contract=off where results are pinned bit for bit: these kernels reproduce float->int truncations
 # of the reference (see input_prep.hip's header) or round step by step like their CPU twins -- and so does every host half ...
-HIP_NO_CONTRACT=" input_prep raster data_prep pil_resize fid_stats grad_guard ema d_augment feature_metrics swd region_metrics gan_loss region_loss "
+HIP_NO_CONTRACT=" input_prep raster data_prep pil_resize fid_stats grad_guard ema d_augment feature_metrics swd region_metrics gan_loss region_loss style_loss "
 # ... except these three
 HOST_CONTRACT=" jpeg_host png_host png_decode_host "
 

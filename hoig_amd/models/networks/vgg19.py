@@ -81,9 +81,11 @@ class VGGLoss(object):
     def cuda(self, *a, **k):
         return self
 
-    def forward_nhwc(self, x, y, scale=1.0, side=None, into=None):
+    def forward_nhwc(self, x, y, scale=1.0, side=None, into=None, style=None):
         """`side`: a stream on which the (gradient-free) features of the target `y` are evaluated beside those of `x`.
-        `into` = ops.LossSlots.term(name): the five levels are added to that slot; returns their handles (for LossSlots.total)."""
+        `into` = ops.LossSlots.term(name): the five levels are added to that slot; returns their handles (for LossSlots.total).
+        `style` = (options of hoig_amd.style_loss, term slot, report slot or None), with `into`: the Gram-matrix term of the chosen
+        levels on the same features, after the L1s and on their stream; its handles follow the five."""
         if side is not None and x.is_cuda:
             main = torch.cuda.current_stream()
             side.wait_stream(main)
@@ -99,7 +101,16 @@ class VGGLoss(object):
             with torch.no_grad():
                 fy = self.vgg.forward_nhwc(y)
         if into is not None:
-            return [ops.l1_loss(a, b, scale=w * scale, into=into) for w, a, b in zip(self.weights, fx, fy)]
+            out = [ops.l1_loss(a, b, scale=w * scale, into=into) for w, a, b in zip(self.weights, fx, fy)]
+            if style is not None:
+                from ...style_loss import style_loss
+                options, slot, raw = style
+                for k, w in zip(options['levels'], options['level_weights']):
+                    if w > 0.0:
+                        out.append(style_loss(fx[k - 1], fy[k - 1], options['weight'] * w, slot, raw))
+            return out
+        if style is not None:
+            raise ValueError('VGGLoss: style= needs into=')
         loss = 0
         for w, a, b in zip(self.weights, fx, fy):
             loss = loss + ops.l1_loss(a, b, scale=w * scale)

@@ -85,6 +85,7 @@ class Trainer(BaseModel):
     _gan = None               # (likewise: the least-squares objective ...)
     _lecam = None             # (... without the LeCam regulariser)
     _region = None            # (likewise: no region reconstruction terms)
+    _style = None             # (likewise: no style term)
 
     def __init__(self, opt, use_ddp=False):
         super(Trainer, self).__init__(opt, use_ddp)
@@ -144,6 +145,13 @@ class Trainer(BaseModel):
         from ..region_loss import parse_options as parse_region_options, active as region_active
         self._region_options = parse_region_options(opt)
         self._region = self._region_options if region_active(self._region_options) else None   # None: ops.l1_loss, launch for launch
+        # the style (Gram-matrix) term of G on the VGG features of the target view (docs/style_loss.md), off by default:
+        # opt.lambda_style / HOIG_LAMBDA_STYLE > 0; opt.style_levels ('2,3,4,5'), opt.style_level_weights (all 1)
+        from ..style_loss import parse_options as parse_style_options, active as style_active
+        self._style_options = parse_style_options(opt)
+        self._style = self._style_options if style_active(self._style_options) else None       # None: VGGLoss's five L1s alone
+        if self._style is not None and self._is_train and not opt.use_vgg:
+            raise ValueError('lambda_style %r needs use_vgg: the style term is taken on the VGG features' % (self._style['weight'],))
 
         self._init_create_networks(use_ddp=use_ddp)
         if self._is_train:
@@ -276,10 +284,11 @@ class Trainer(BaseModel):
         if self._opt.use_vgg:
             self._crt_tsf = VGGLoss(vgg=vgg_net)
         # the terms of the two objectives live in device slots that the loss kernels add into (ops.LossSlots)
+        style = ['g_style'] if self._style is not None else []
         if self._region is None:
-            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth'], self.device)
+            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth'] + style, self.device)
         else:       # (the report slots of L_0, L_1, L_2 lie side by side: the head adds to all three, the background's is not reported)
-            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth', 'g_rec_region'], self.device,
+            self._g_terms = ops.LossSlots(['g_adv', 'g_rec', 'g_tsf', 'g_mask', 'g_mask_smooth', 'g_rec_region'] + style, self.device,
                                           extra=['g_rec_bg', 'g_rec_hand', 'g_rec_obj'])
         self._d_terms = ops.LossSlots(['d'], self.device, extra=['d_real', 'd_fake'] + (['d_reg'] if self._lecam is not None else []))
         z = lambda: torch.zeros((), device=self.device)
@@ -762,7 +771,11 @@ class Trainer(BaseModel):
         else:
             rec = self._region_losses(fake_src, fake_tsf)
         # the reference uses self._crt_tsf in both branches of `if use_vgg` (:443-446); it only exists with --use_vgg
-        tsf = self._crt_tsf.forward_nhwc(fake_tsf, n['real_tsf'], o.lambda_tsf, side=s_vgg, into=into('g_tsf'))
+        if self._style is None:
+            tsf = self._crt_tsf.forward_nhwc(fake_tsf, n['real_tsf'], o.lambda_tsf, side=s_vgg, into=into('g_tsf'))
+        else:       # (the Gram-matrix term of the chosen levels, on the same features: docs/style_loss.md)
+            tsf = self._crt_tsf.forward_nhwc(fake_tsf, n['real_tsf'], o.lambda_tsf, side=s_vgg, into=into('g_tsf'),
+                                             style=(self._style, into('g_style'), None))
         if fork:
             main.wait_stream(s_adv)
         crt = ops.bce_loss if o.mask_bce else ops.mse_loss
@@ -889,6 +902,8 @@ class Trainer(BaseModel):
         if self._region is not None:                  # (the objective's region slot; the unweighted L_hand and L_obj over the views)
             for k in ('g_rec_region', 'g_rec_hand', 'g_rec_obj'):
                 out[k] = self._g_terms.value(k).item()
+        if self._style is not None:                   # (the objective's style slot: lambda_style sum_l w_l L_l)
+            out['g_style'] = self._g_terms.value('g_style').item()
         return out
 
     def grad_report(self):

@@ -1169,6 +1169,36 @@ int hoig_region_loss_host(const float *pred, const float *target, const uint8_t 
                           const double *lambda, double lambda_all, int min_pixels, float *dpred, float *term, float *terms_r,
                           float *term_all, int32_t *counts_out, int32_t *status);
 
+/* ---- OPT-IN STYLE (GRAM-MATRIX) TERM FOR G (hoig_amd/csrc/style_loss.hip, style_loss.h, style_loss_host.cpp; hoig_amd/style_loss.py;
+ *      docs/style_loss.md).  fx, fy: fp32 [N][P][C], the NHWC features of one VGG level with P = H W.  Per image n:
+ *        G(F)[n] = F[n]^T F[n] / (C P)                                  (C x C)
+ *        L       = (1 / (N C^2)) sum_{n,i,j} |G(fx) - G(fy)|
+ *        S[n]    = sign(G(fx)[n] - G(fy)[n]) (float)(2 scale / (N C^3 P))   (symmetric; sign(0) = 0, and 0 for a NaN difference)
+ *        *term   += (float)(scale L),  *report += (float)L                 (either may be NULL)
+ *        gram    = G(fx)[0 .. N), G(fy)[0 .. N) in double                  ([2N][C][C]; may be NULL)
+ *        dfx[n]  = fx[n] S[n] = d(scale L) / d fx[n]                       (hoig_style_dfeat; fy gets no gradient)
+ *      The Gram pass is split over tile pairs tj >= ti of HOIG_STYLE_TILE channels and over chunks of HOIG_STYLE_CHUNK pixels: every entry
+ *      of a chunk's partial tile is an fp32 fma chain from +0 over the chunk's pixels in ascending order (v_mfma_f32_32x32x2_f32); the
+ *      chunks are added in index order in double, and |d| in double in an order fixed by (N, P, C).  Every element of dfx is an fp32
+ *      fma chain from +0 over the channels in ascending order.  No atomics, no wait between workgroups; three launches (gram) and one
+ *      (dfeat) on `stream`; never synchronises, allocates nothing.  The *_host twins take host memory, make no HIP call and give the
+ *      device's bits.  Nothing is launched and HOIG_EUNSUPPORTED is returned for N above HOIG_STYLE_MAX_N, P above HOIG_STYLE_MAX_P, or a C
+ *      that is no multiple of 16 in 16 .. HOIG_STYLE_MAX_C; HOIG_EINVAL for N, P or C below 1, a NULL or misaligned pointer (fx, fy, S,
+ *      dfx, gram, workspace: 16 bytes; term, report: 4), a negative or non-finite scale, a short workspace, an S or gram that overlaps
+ *      an input or each other, or a dfx that overlaps fx or S. ---- */
+#define HOIG_STYLE_TILE 64        /* channels of a Gram tile's edge, and columns of a gradient tile */
+#define HOIG_STYLE_CHUNK 1024     /* pixels of one Gram partial: the longest fma chain of the Gram pass */
+#define HOIG_STYLE_MAX_N 4096     /* the most images of a call */
+#define HOIG_STYLE_MAX_P 4194304  /* the most pixels of an image (2^22) */
+#define HOIG_STYLE_MAX_C 512      /* the most channels */
+int64_t hoig_style_workspace_bytes(int N, int P, int C);
+int hoig_style_gram(const float *fx, const float *fy, int N, int P, int C, double scale, float *S, float *term, float *report,
+                    double *gram, void *workspace, int64_t workspace_bytes, hoig_stream_t stream);
+int hoig_style_dfeat(const float *fx, const float *S, int N, int P, int C, float *dfx, hoig_stream_t stream);
+int hoig_style_gram_host(const float *fx, const float *fy, int N, int P, int C, double scale, float *S, float *term, float *report,
+                         double *gram);
+int hoig_style_dfeat_host(const float *fx, const float *S, int N, int P, int C, float *dfx);
+
 #ifdef __cplusplus
 }
 #endif
