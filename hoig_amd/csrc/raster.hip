@@ -4,7 +4,8 @@
 //
 // The reference tests EVERY face at EVERY pixel (256 x 256 x ~15 k faces per view, twice per sample).  Here:
 //   setup : one thread per face -- back-face test, the inverse edge matrix, and a conservative bounding box in 16 x 16-pixel
-//           tiles (one pixel of slack on every side; faces with non-finite vertices get the whole image);
+//           tiles (raster_box.h: one pixel of slack on every side; faces with non-finite vertices, and slivers whose fp32
+//           edge tests can pass outside that box, get the whole image; docs/raster_parity.md);
 //   tiles : one 256-thread workgroup per tile and image.  It streams the packed boxes of all faces (4 B each, coalesced),
 //           gathers the records of the faces that touch the tile into LDS (unordered, LDS atomic counter) and every thread
 //           -- one pixel -- runs the reference's per-face test only over that list, reading records as LDS broadcasts.
@@ -13,16 +14,11 @@
 // for literal (its unsuffixed constants are doubles); the file is compiled with -ffp-contract=off (as the CPU
 // restatement it is tested against), because an FMA in an edge function moves pixels across a triangle's border.
 #include "common.h"
+#include "raster_box.h"
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int TILE = 16, NT = TILE * TILE, REC = 20, CAP = 512;
-
-constexpr unsigned EMPTY_BOX = 0x00ff00ffu;            // tx0 = 255 > tx1 = 0: never overlaps
-
-__device__ inline bool back_side(const float *f) {    // rasterize_cuda_kernel.cu:55,127
-    return (f[7] - f[1]) * (f[3] - f[0]) < (f[4] - f[1]) * (f[6] - f[0]);
-}
+constexpr int TILE = RB_TILE, NT = TILE * TILE, REC = 20, CAP = 512;
 
 __global__ void raster_setup_kernel(const float *__restrict__ faces, int n_faces_total, int is, float *__restrict__ rec,
                                     unsigned *__restrict__ box) {
@@ -31,8 +27,8 @@ __global__ void raster_setup_kernel(const float *__restrict__ faces, int n_faces
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = faces[(size_t)i * 9 + k];
-    if (back_side(f)) {
-        box[i] = EMPTY_BOX;
+    if (raster_back_side(f)) {
+        box[i] = RB_EMPTY_BOX;
         return;
     }
     float p[3][2];                                     // :59-63: [-1,1] -> [0, is-1]
@@ -49,24 +45,7 @@ __global__ void raster_setup_kernel(const float *__restrict__ faces, int n_faces
     for (int k = 0; k < 9; ++k) r[k] = f[k];
 #pragma unroll
     for (int k = 0; k < 9; ++k) r[9 + k] = m[k] / den;
-    // bounding box in pixels (p is the pixel-space vertex), one pixel of slack, then in tiles
-    const float lox = fminf(p[0][0], fminf(p[1][0], p[2][0])), hix = fmaxf(p[0][0], fmaxf(p[1][0], p[2][0]));
-    const float loy = fminf(p[0][1], fminf(p[1][1], p[2][1])), hiy = fmaxf(p[0][1], fmaxf(p[1][1], p[2][1]));
-    const int last = (is - 1) / TILE;
-    unsigned b;
-    const bool finite = isfinite(p[0][0]) && isfinite(p[1][0]) && isfinite(p[2][0]) && isfinite(p[0][1]) && isfinite(p[1][1]) &&
-                        isfinite(p[2][1]);
-    if (!finite) {
-        b = 0u | ((unsigned)last << 8) | (0u << 16) | ((unsigned)last << 24);
-    } else if (hix < -1.f || hiy < -1.f || lox > (float)is || loy > (float)is) {
-        b = EMPTY_BOX;
-    } else {
-        const int x0 = max((int)floorf(fmaxf(lox, -1.f)) - 1, 0) / TILE, y0 = max((int)floorf(fmaxf(loy, -1.f)) - 1, 0) / TILE;
-        const int x1 = min((int)ceilf(fminf(hix, (float)is)) + 1, is - 1) / TILE;
-        const int y1 = min((int)ceilf(fminf(hiy, (float)is)) + 1, is - 1) / TILE;
-        b = (unsigned)x0 | ((unsigned)x1 << 8) | ((unsigned)y0 << 16) | ((unsigned)y1 << 24);
-    }
-    box[i] = b;
+    box[i] = raster_face_box(f, is);
 }
 
 __global__ __launch_bounds__(NT) void raster_tile_kernel(const float *__restrict__ rec, const unsigned *__restrict__ box, int F,
@@ -223,7 +202,8 @@ extern "C" int hoig_project_faces(const float *cam, int cam_dim, const float *ve
     ProjArgs a;
     a.cam = cam; a.verts = verts; a.B = B; a.V = V; a.cam_dim = cam_dim; a.Fmax = Fmax; a.eye_z = eye_z; a.pad = pad_value; a.out = faces_out;
     for (int b = 0; b < B; ++b) {
-        if (!face_lists[b] || n_faces[b] < 0 || n_faces[b] > Fmax) return HOIG_EINVAL;
+        // (a sample without faces may bring no list: an empty tensor has no address, and the kernel reads none of it)
+        if ((!face_lists[b] && n_faces[b] != 0) || n_faces[b] < 0 || n_faces[b] > Fmax) return HOIG_EINVAL;
         a.faces[b] = reinterpret_cast<const long long *>(face_lists[b]);
         a.nf[b] = n_faces[b];
     }

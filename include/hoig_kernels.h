@@ -525,12 +525,16 @@ size_t hoig_rasterize_workspace_bytes(int B, int F);
  * utils/nmr.py:109-140: cam_dim 15 = 3x3 camera matrix | 2x3 crop transform; HOIG_DexYCB/utils/nmr.py:146-163: cam_dim 10 = fx, fy, cx,
  * cy | crop transform), the y flip (:506), nr.look_at with the renderer's eye (z - eye_z) and nr.vertices_to_faces (:508-511).
  * verts [B][V][3]; face_lists: HOST array of B device pointers to [n_faces[b]][3] int64 vertex indices (a sample's object decides its
- * list), n_faces: host array; faces_out [B][Fmax][3][3], rows >= n_faces[b] filled with pad_value (a point no pixel can see).
+ * list; it may be null where n_faces[b] is 0), n_faces: host array; faces_out [B][Fmax][3][3], rows >= n_faces[b] filled with pad_value (a point no pixel can see).
  * B <= HOIG_PREP_MAX_BATCH. */
 int hoig_project_faces(const float *cam, int cam_dim, const float *verts, int V, const int64_t *const *face_lists, const int *n_faces,
                        int B, int Fmax, float eye_z, float pad_value, float *faces_out, hoig_stream_t stream);
 int hoig_rasterize_fim_wim(const float *faces, int B, int F, int image_size, float near, float far, int32_t *fim,
                            float *wim, void *workspace, hoig_stream_t stream);
+/* The CPU twin of the rasteriser's setup stage (hoig_amd/csrc/raster_box.h, raster_host.cpp; docs/raster_parity.md): the packed tile
+ * box x0 | x1 << 8 | y0 << 16 | y1 << 24 (16 x 16-pixel tiles) inside which the tile kernel tests each of n_faces faces [n][3][3];
+ * 0x00ff00ff: in no tile (a back face, or off screen).  Host memory only. */
+int hoig_raster_face_boxes_host(const float *faces, int n_faces, int image_size, uint32_t *boxes_out);
 
 /* ---- data loader, device side: the image work of HOv3Dataset._get_sample (HOIG_HOv3/data/hov3_dataset.py:215-223,
  *      63-91) and of __getitem__'s transform (:208-212,267) for a batch of decoded 8-bit frames.  Both replace calls into

@@ -13,10 +13,13 @@
  * reproduced (compiled with -ffp-contract=off, as the HIP kernel is).  tests/test_raster_oracle.py checks this file against
  * geometric ground truth (known triangles, exact barycentric weights, depth order, back-face and near/far culling).
  */
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
-static float clamp01(float v) { return (float)(v < 0. ? 0. : (v > 1. ? 1. : (double)v)); }   /* min(max(w, 0.), 1.)  :146 */
+/* min(max(w, 0.), 1.)  :146: the double literals pick CUDA's fmax / fmin, which return the other operand for a NaN: NaN -> 0 */
+static float clamp01(float v) { return (float)fmin(fmax((double)v, 0.), 1.); }
+float oracle_raster_clamp01(float v) { return clamp01(v); }            /* for tests/test_raster_oracle.py */
 
 /* faces [B][F][3][3] (x, y, z per vertex; x, y in [-1,1] normalised image coordinates, y up), outputs fim [B][S][S]
  * (int32, -1 = no face), wim [B][S][S][3]; scratch faces_inv [B][F][9] */

@@ -131,3 +131,49 @@ def synthetic_mesh_faces(batch, n_random=1500, seed=5):
             rnd[10:20, :, :2] = g.uniform(-0.2, 0.2, size=(1, 3, 2)) + g.uniform(-0.01, 0.01, size=(10, 3, 2))
         out.append(np.concatenate([sphere, rnd], 0).astype(np.float32))
     return torch.from_numpy(np.stack(out))
+
+
+def raster_boxes_host(faces, image_size):
+    """faces (..., 3, 3) float32 array or tensor -> the packed tile boxes (uint32, one per face) of the rasteriser's setup stage by
+    its CPU twin (hoig_raster_face_boxes_host: hoig_amd/csrc/raster_box.h, the function raster_setup_kernel calls)."""
+    from hoig_amd import _lib as L
+    f = np.ascontiguousarray(faces.numpy() if torch.is_tensor(faces) else faces, dtype=np.float32).reshape(-1, 9)
+    out = np.empty(f.shape[0], np.uint32)
+    if not len(out):
+        return out
+    L.call('hoig_raster_face_boxes_host', f.ctypes.data, f.shape[0], int(image_size), out.ctypes.data)
+    return out
+
+
+def pixel_centre(i, S):
+    """The rasteriser's own coordinate of pixel i (rasterize_cuda_kernel.cu:112-113): (2 i + 1 - S) / S in double, rounded to fp32."""
+    return ((2.0 * np.asarray(i, np.float64) + 1 - S) / S).astype(np.float32)
+
+
+def sliver_faces(S, n, seed, on_centres=True):
+    """(n,3,3) float32 slivers: faces whose two long edges differ in direction by a few ulps, so that both edge tests round to 'not
+    outside' along the line through the face (docs/raster_parity.md).  Two vertices on pixel centres, a step of {-2..2}^2 times 2..9 pixels apart
+    (or, on_centres=False, at arbitrary points of such a line through one pixel centre), one end sometimes outside the image; the third on the
+    segment at a fraction in [0.05, 0.5], nudged by -2..+2 ulps on one coordinate; vertex order permuted; depths in [1, 3]."""
+    g = np.random.default_rng([seed, S, int(on_centres)])
+    step = g.integers(-2, 3, size=(n, 2))
+    step[(step == 0).all(1)] = (1, 2)
+    step = step * g.integers(2, 10, size=(n, 1))
+    i0 = g.integers(-3, S + 3, size=(n, 2))
+    if on_centres:
+        v0, v1 = pixel_centre(i0, S), pixel_centre(i0 + step, S)
+    else:                       # on the lattice line through pixel i0, at real multiples of the step: off it by their own rounding
+        c = (2.0 * i0 + 1 - S) / S
+        v0 = (c + g.uniform(-0.9, -0.1, size=(n, 1)) * step * (2.0 / S)).astype(np.float32)
+        v1 = (c + g.uniform(0.1, 0.9, size=(n, 1)) * step * (2.0 / S)).astype(np.float32)
+    t = g.uniform(0.05, 0.5, size=(n, 1)).astype(np.float32)
+    v2 = (v0 + t * (v1 - v0)).astype(np.float32)
+    axis, ulps = g.integers(0, 2, size=n), g.integers(-2, 3, size=n)
+    for k in (1, 2):                                                  # |ulps| steps of nextafter on the chosen coordinate
+        sel = np.abs(ulps) >= k
+        v2[sel, axis[sel]] = np.nextafter(v2[sel, axis[sel]], np.where(ulps[sel] > 0, np.float32(np.inf), np.float32(-np.inf)))
+    xy = np.stack([v0, v1, v2], 1)
+    order = np.argsort(g.uniform(size=(n, 3)), axis=1)
+    xy = np.take_along_axis(xy, order[:, :, None], axis=1)
+    z = g.uniform(1.0, 3.0, size=(n, 3, 1)).astype(np.float32)
+    return np.concatenate([xy, z], -1).astype(np.float32)

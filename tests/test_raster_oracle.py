@@ -123,3 +123,26 @@ def test_vertex_stage_matches_reference_live():
     # picks the batch axis -- a quirk the reference never meets, render_fim_wim is called per sample)
     ref = torch.from_numpy(np.load(os.path.join(here, 'golden', 'raster_vertex_stage_seed7.npz'))['faces'])
     assert torch.equal(raster.project_to_faces(cam, verts, idx), ref)
+
+
+def test_weight_clamp_drops_nan_like_the_reference():
+    """rasterize_cuda_kernel.cu:146 clamps with min(max(w, 0.), 1.): the double literals pick fmax / fmin, which return the other
+    operand for a NaN, so a NaN weight becomes 0 -- it does not stay NaN, as a chain of comparisons would leave it.  (The HIP kernel
+    says fmin / fmax too.)  On exactly collinear faces through pixel centres, whose weights are 0 / 0 and x / 0, this shows in no
+    output: they cover nothing."""
+    import ctypes
+    import os
+    from common import GOLDEN_DIR, pixel_centre
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(GOLDEN_DIR), os.pardir, 'oracle', '_build', 'libhoig_oracle_c.so'))
+    lib.oracle_raster_clamp01.argtypes, lib.oracle_raster_clamp01.restype = [ctypes.c_float], ctypes.c_float
+    c = lib.oracle_raster_clamp01
+    assert c(float('nan')) == 0.0
+    assert [c(v) for v in (-np.inf, -3.0, 0.0, 0.25, 1.0, 1.5, np.inf)] == [0.0, 0.0, 0.0, 0.25, 1.0, 1.0, 1.0]
+    g = np.random.default_rng(6)
+    n = 500
+    i0, step = g.integers(0, S, size=(n, 2)), g.integers(-2, 3, size=(n, 2))
+    k = np.sort(g.integers(-6, 7, size=(n, 3)), axis=1)                   # three points of one lattice line, two of them equal at times
+    xy = pixel_centre(i0[:, None, :] + k[:, :, None] * step[:, None, :], S)
+    f = np.concatenate([xy, g.uniform(1, 3, size=(n, 3, 1)).astype(np.float32)], -1)
+    fim, wim = oracle_rasterize(torch.from_numpy(f[:, None]), S)
+    assert (fim == -1).all() and not wim.any()
